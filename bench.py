@@ -10,6 +10,11 @@ env ids (weak scaling, no data-path collective: the headline), and the line's `s
 BASELINE configs[3] as stated, 32,768 envs in total split over the ranks (`--scaling`); barrier +
 synchronize bracket every timed region and the max over ranks is reported.
 
+A plain run sets up, warms up, times `--steps` steps and prints the headline line (`ms_per_step` is
+the time of one timed step); `--dump-outputs DIR` also writes what the last timed step returned.
+Everything else below (per-launch durations and rooflines, the episode-ahead, rollout, configs[1],
+configs[4] and strong-scaling objects, the CPU baseline) is measured under `--full` only.
+
 Roofline: average device duration of each kernel measured with HIP events on the launch stream
 (torch's current stream); algorithmic bytes per launch from the state layout.
 cpu_baseline: the C oracle (oracle/, a scalar port of the reference) timed on the host cores on a
@@ -126,9 +131,41 @@ def bench_obs_stats(cfg, meta, n_episodes: int = 2):
     return compute_obs_statistics(cfg, SeedManager(42), "meanstd_custom", n_episodes=n_episodes, env_meta=meta)
 
 
-def time_env(env, pool, steps: int, warmup: int, world: int, ea: bool = False):
-    """warmup untimed steps, then `steps` timed ones (barrier + synchronize on both sides); then a
-    timing pass of min(steps, 50) steps with the library's per-launch HIP events."""
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000  # --dump-outputs writes at most this much in all
+
+
+def snapshot_outputs(res) -> dict:
+    """What the last env.step() handed its caller (observations, rewards, truncation flags, final
+    observations), as float32 arrays on the host. The tensors are the env's own buffers, which the
+    next step overwrites, so this runs right after the timed window. Over DUMP_BUDGET_BYTES in all,
+    every array keeps the same fixed, seeded sample of envs (sorted ids, also written as `env_ids`)."""
+    import numpy as np
+    import torch
+    names = ("obs", "rewards", "truncated", "final_obs")
+    tens = {n: t for n, t in zip(names, res) if t is not None}
+    E = next(iter(tens.values())).shape[0]
+    per_env = sum(t[0].numel() for t in tens.values()) * 4 + 8
+    keep = min(E, DUMP_BUDGET_BYTES // per_env)
+    ids = np.arange(E) if keep == E else np.sort(np.random.default_rng(0).choice(E, keep, replace=False))
+    idx = torch.from_numpy(ids).to(next(iter(tens.values())).device)
+    out = {n: t.index_select(0, idx).to(torch.float32).cpu().numpy() for n, t in tens.items()}
+    out["env_ids"] = ids.astype(np.float64)
+    return out
+
+
+def write_outputs(dump_dir: str, arrays: dict) -> None:
+    import numpy as np
+    d = Path(dump_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_BUDGET_BYTES
+    for name, a in arrays.items():
+        np.save(d / f"{name}.npy", a)
+
+
+def time_env(env, pool, steps: int, warmup: int, world: int, ea: bool = False, detail: bool = True, snapshot=None):
+    """warmup untimed steps, then `steps` timed ones (barrier + synchronize on both sides). With
+    `detail` (--full) then a timing pass of min(steps, 50) steps with the library's per-launch HIP
+    events and the host-enqueue bursts. `snapshot` (a dict) receives the last timed step's outputs."""
     import torch
     import torch.distributed as dist
     for i in range(warmup):
@@ -138,9 +175,10 @@ def time_env(env, pool, steps: int, warmup: int, world: int, ea: bool = False):
         dist.barrier()
     torch.cuda.synchronize()
     w0 = env.work_counters()
+    res = None
     t0 = time.perf_counter()
     for i in range(steps):
-        env.step(pool[i % len(pool)])
+        res = env.step(pool[i % len(pool)])
     t_host = time.perf_counter() - t0  # the host's enqueue time (the device may still be busy)
     torch.cuda.synchronize()
     if world > 1:
@@ -148,6 +186,10 @@ def time_env(env, pool, steps: int, warmup: int, world: int, ea: bool = False):
     dt = time.perf_counter() - t0
     w1 = env.work_counters()
     env.check()
+    if snapshot is not None and res is not None:
+        snapshot.update(snapshot_outputs(res))
+    if not detail:
+        return dt, {"enqueue_ms_per_step": t_host / steps * 1e3, "window": window_work(w0, w1, env.n_envs, steps)}
     # the timing pass: 50 steps, or with episode-ahead demand 2.5 episodes (a generation launch covers
     # whole episodes of every env: one or two per episode in steady state)
     kp = min(steps, 50) if not ea else int(2.5 * env.spec.episode_length)
@@ -522,6 +564,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--warmup", type=int, default=100)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: per-launch kernel durations and rooflines, the episode-ahead line, "
+                         "the MAPPO rollout, the GAE and MLP kernels alone, the configs[1] / configs[4] lines, the "
+                         "strong-scaling object at N > 1 and the CPU baseline (the other options below select among these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step of the headline returned (obs, rewards, truncated, final_obs "
+                         "of a fixed seeded sample of envs, and their env_ids) as DIR/<name>.npy, float32 / float64")
     ap.add_argument("--config", choices=("c3", "c5"), default="c3",
                     help="c3: BASELINE configs[2]/[3] (8 x 64 x 5, Poisson, 32768 envs, default); c5: configs[4] "
                          "(16 x 256 x 5, empirical trace of ~200-1,000 orders per step, 8192 envs)")
@@ -552,6 +601,10 @@ def main():
                     help="env handles the rollout's envs are split into, each stepping on its own HIP stream so one "
                          "lane's env kernels overlap another's policy GEMMs (1 = one handle, one stream)")
     args = ap.parse_args()
+    if not args.full:  # a plain run times the headline alone
+        if args.scaling == "strong":
+            ap.error("--scaling strong is measured under --full")
+        args.rollout_T, args.c2_envs, args.c5_envs, args.no_cpu_baseline = 0, 0, 0, True
 
     import torch
     import torch.distributed as dist
@@ -616,15 +669,19 @@ def main():
     #     side stream behind the step kernel of step t, see msc_env_step), then (2) per-launch device
     #     durations for the roofline in the same regime: the library brackets each demand launch and
     #     each step launch (step_a/b/c) with HIP events on the stream it runs on (msc_env_set_timing)
-    dt, tm = time_env(env, pool, K, args.warmup, world)
-    t_demand, t_step = tm["demand_ms"] / 1e3, tm["step_ms"] / 1e3
+    #     (--full only, as every numbered measurement below)
+    dumped = {} if args.dump_outputs and rank == 0 else None
+    dt, tm = time_env(env, pool, K, args.warmup, world, detail=args.full, snapshot=dumped)
+    if dumped:
+        write_outputs(args.dump_outputs, dumped)
+    t_demand, t_step = tm.get("demand_ms", 0.0) / 1e3, tm.get("step_ms", 0.0) / 1e3
     # (1b) the same envs in episode-ahead steady state: whole future episodes of
     #      every env generated on the library's side stream while earlier ones step; a generation
     #      launch refills one slot per episode, so the window is whole episodes after the pipeline
     #      has filled (6 episodes of warm-up, 8 timed); every timed step's demand is generated inside
     #      the window in steady state
     ea_line = None
-    if want_ea and env.ea_slots:
+    if args.full and want_ea and env.ea_slots:
         T_ep = spec.episode_length
         env.set_episode_ahead(True)
         dt_ea, tm_ea = time_env(env, pool, 8 * T_ep, 6 * T_ep, 1, ea=True)
@@ -644,7 +701,7 @@ def main():
     # episode-ahead demand (the library's default): the demand work of the timed
     # steps runs as generation launches of whole episodes on a side stream; per launch its duration
     # and the env-steps it generated
-    ea_regime = tm["n_ea"] > 0 and tm["ea_env_steps_per_launch"] > 0
+    ea_regime = args.full and tm["n_ea"] > 0 and tm["ea_env_steps_per_launch"] > 0
     t_ea = tm["ea_ms"] / 1e3 if ea_regime else 0.0
     ea_work = tm["ea_env_steps_per_launch"] if ea_regime else 0.0
     # (3) MAPPO rollout (configs[2]): env step + actor/critic forward + sampling + buffer writes +
@@ -732,7 +789,7 @@ def main():
             del xg, yo
     # (6) N > 1: BASELINE configs[3] as stated, the same 32,768 envs split over the ranks (strong)
     strong = None
-    if world > 1 and args.scaling in ("strong", "both") and args.config == "c3":
+    if args.full and world > 1 and args.scaling in ("strong", "both") and args.config == "c3":
         env.close()
         strong = strong_line(args, rank, world, spec, meta)
     c2 = None
@@ -751,6 +808,35 @@ def main():
         value = E * world * spec.W * K / dt
         mean_orders = (float(spec.trace["offsets"][-1]) / spec.trace["n_rows"] if spec.demand_type == "empirical"
                        else float(spec.lambda_orders.sum()))
+        # the result line of a plain run; --full adds the objects built below to it
+        out = {
+            "metric": BASELINE["metric"],
+            "value": round(value, 1),
+            "unit": "agent-steps/s",
+            "n_gpus": world,
+            "steps": K,
+            "warmup": args.warmup,
+            "ms_per_step": round(dt / K * 1e3, 4),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "window": tm["window"],
+            "dtype": "int32 state, u64 PCG64, f64 rewards, f32 obs",
+            "data": ("synthetic (SURVEY.md 8(d) cost structure, Poisson demand lambda_o=4 p=0.667 lambda_q=5, uniform[-1,1] actions)"
+                     if args.config == "c3" else
+                     f"synthetic (SURVEY.md 8(d) cost structure; empirical demand: a synthetic preprocessor frame of 300 timesteps, "
+                     f"{mean_orders:.0f} orders per step on average over 256 regions; uniform[-1,1] actions)"),
+            "config": {"workload": f"InventoryEnvironment.step x {E} envs/GPU, {spec.W} agents x {spec.R} regions x "
+                                   f"{spec.K} SKUs " + ("(BASELINE configs[2]; configs[3] when N>1)" if args.config == "c3"
+                                                        else "(BASELINE configs[4], empirical trace)"),
+                       "n_envs_per_gpu": E, "agents": spec.W, "regions": spec.R, "skus": spec.K,
+                       "episode_length": spec.episode_length, "obs_dim_local": spec.local_obs_dim,
+                       "obs_normalization": meta.get("obs_normalization", "off"), "parallelism": f"env-shard x{world}"},
+            "enqueue_ms_per_step": round(tm["enqueue_ms_per_step"], 4),
+        }
+        if not args.full:
+            print(json.dumps(out))
+    if rank == 0 and args.full:
         b_dem, b_step = algorithmic_bytes(spec, mean_orders)
         # per launch: (duration, algorithmic bytes, duration per step of the workload) -- the dominant
         # kernel is the one with the most device time per step
@@ -795,33 +881,11 @@ def main():
                 step_valu = issue_object(tot, dt / K, None, insts_per_step=int(tot), kernels=list(names_all))
         achieved = bytes_dom / t_dom / 1e9
         out = {
-            "metric": BASELINE["metric"],
-            "value": round(value, 1),
-            "unit": "agent-steps/s",
-            "n_gpus": world,
-            "steps": K,
-            "warmup": args.warmup,
-            "ms_per_step": round(dt / K * 1e3, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "window": tm["window"],
-            "dtype": "int32 state, u64 PCG64, f64 rewards, f32 obs",
-            "data": ("synthetic (SURVEY.md 8(d) cost structure, Poisson demand lambda_o=4 p=0.667 lambda_q=5, uniform[-1,1] actions)"
-                     if args.config == "c3" else
-                     f"synthetic (SURVEY.md 8(d) cost structure; empirical demand: a synthetic preprocessor frame of 300 timesteps, "
-                     f"{mean_orders:.0f} orders per step on average over 256 regions; uniform[-1,1] actions)"),
-            "config": {"workload": f"InventoryEnvironment.step x {E} envs/GPU, {spec.W} agents x {spec.R} regions x "
-                                   f"{spec.K} SKUs " + ("(BASELINE configs[2]; configs[3] when N>1)" if args.config == "c3"
-                                                        else "(BASELINE configs[4], empirical trace)"),
-                       "n_envs_per_gpu": E, "agents": spec.W, "regions": spec.R, "skus": spec.K,
-                       "episode_length": spec.episode_length, "obs_dim_local": spec.local_obs_dim,
-                       "obs_normalization": meta.get("obs_normalization", "off"), "parallelism": f"env-shard x{world}"},
+            **out,
             "kernels_ms": {DEMAND_KERNEL: round(t_demand * 1e3, 4), "step_kernels": round(t_step * 1e3, 4),
                            **({DEMAND_KERNEL + "_ea": round(t_ea * 1e3, 3), "ea_env_steps_per_launch": int(ea_work),
                                "ea_slots": tm["slots"]} if ea_regime else {})},
             "host_ms_per_step": round(tm["host_ms_per_step"], 4),
-            "enqueue_ms_per_step": round(tm["enqueue_ms_per_step"], 4),
             "roofline": {"kernel": dom, "bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
                          "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
                          "traffic": traffic, "bytes_per_launch": int(bytes_dom),

@@ -18,7 +18,7 @@ for rep in $(seq 1 ${REPS:-1}); do
   for v in ${VARIANTS:-default=}; do
     name=${v%%=*}; assigns=${v#*=}
     ( IFS=,; for a in $assigns; do [ -n "$a" ] && export "$a"; done; unset IFS
-      timeout -k 10 ${T_BENCH:-300} python bench.py --steps ${STEPS:-1000} --warmup ${WARMUP:-100} --no-cpu-baseline \
+      timeout -k 10 ${T_BENCH:-300} python bench.py --full --steps ${STEPS:-1000} --warmup ${WARMUP:-100} --no-cpu-baseline \
         --rollout-T ${ROLLOUT_T:-0} ${BENCH_ARGS:-} > gpurun_out/ab_${name}_$rep.log 2>&1 )
     rc=$?
     echo "== $name rep $rep rc=$rc $(tail -n 1 gpurun_out/ab_${name}_$rep.log | python3 -c 'import json,sys

@@ -11,6 +11,6 @@ export TMPDIR=/tmp
 n=${NPROC:-4}
 out=${OUT:-dist_rehearsal_n$n}
 MSC_DIST_BACKEND=gloo timeout -k 10 ${T_DIST:-500} python -m torch.distributed.run --nnodes=1 --nproc-per-node $n \
-  --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus $n --envs ${ENVS:-8192} --steps ${STEPS:-200} --warmup 20 \
+  --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus $n --envs ${ENVS:-8192} --steps ${STEPS:-200} --warmup 20 \
   --rollout-T ${ROLLOUT_T:-100} --scaling ${SCALING:-both} > gpurun_out/$out.json.log 2>&1
 rc=$?; echo "rc=$rc"; tail -n 1 gpurun_out/$out.json.log | cut -c1-600; exit $rc

@@ -10,6 +10,7 @@ ok $rc || exit $rc
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/smoke.log 2>&1
 rc=$?; echo "smoke rc=$rc"; tail -n 3 gpurun_out/smoke.log
 [ $rc -eq 0 ] || [ $rc -eq 1 ] || exit $rc
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # the whole line: rollouts, C2, C5, rooflines, CPU baseline
 timeout -k 10 ${T_BENCH:-600} python bench.py ${BENCH_ARGS:-} > gpurun_out/bench.log 2>&1
 rc=$?; echo "bench rc=$rc"; tail -n 3 gpurun_out/bench.log
 exit $rc

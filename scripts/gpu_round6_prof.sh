@@ -10,6 +10,6 @@ if [ "${RUN_TESTS:-1}" = 1 ]; then
   rc=$?; echo "pytest rc=$rc"; tail -n 3 gpurun_out/pytest_gpu_r06p.log; [ $rc -eq 0 ] || exit $rc
 fi
 R=${R:-r06} timeout -k 10 2400 bash scripts/gpu_profile_all.sh || exit $?
-TAG=${R:-r06}c3ea PMC_ONLY=demand_v3_kernel_ea ARGS="--steps 30 --warmup 3 --no-cpu-baseline --rollout-T 0 --c2-envs 0 --c5-envs 0 --scaling weak" \
+TAG=${R:-r06}c3ea PMC_ONLY=demand_v3_kernel_ea ARGS="--full --steps 30 --warmup 3 --no-cpu-baseline --rollout-T 0 --c2-envs 0 --c5-envs 0 --scaling weak" \
   timeout -k 10 1200 bash scripts/gpu_profile.sh > /dev/null || exit $?
 echo "c3ea done"

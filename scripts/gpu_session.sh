@@ -18,12 +18,13 @@ if [ -n "${VARIANTS:-}" ]; then
 fi
 if [ "${DIST:-0}" = 1 ]; then
   MSC_DIST_BACKEND=gloo timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-    --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --envs ${DIST_ENVS:-8192} --steps 200 --warmup 20 \
+    --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 2 --envs ${DIST_ENVS:-8192} --steps 200 --warmup 20 \
     --rollout-T 20 > gpurun_out/${tag}_dist.log 2>&1
   rc=$?; echo "dist rc=$rc"; tail -n 1 gpurun_out/${tag}_dist.log | cut -c1-400
   [ $rc -eq 0 ] || exit $rc
 fi
 if [ "${BENCH:-0}" = 1 ]; then
+  FINAL_ARGS="--full ${FINAL_ARGS:-}"  # the whole line: rollouts, C2, C5, rooflines, CPU baseline
   timeout -k 10 ${T_BENCH:-600} python bench.py ${FINAL_ARGS:-} > gpurun_out/${tag}_bench.log 2>&1
   rc=$?; echo "bench rc=$rc"; tail -n 1 gpurun_out/${tag}_bench.log | cut -c1-600
   [ $rc -eq 0 ] || exit $rc

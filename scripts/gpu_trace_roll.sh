@@ -4,7 +4,7 @@
 set -u
 mkdir -p gpurun_out
 export TMPDIR=/tmp
-ARGS=${ARGS:-"--steps 10 --warmup 3 --no-cpu-baseline --rollout-T 100 --c2-envs 0 --c5-envs 0 --no-ea-line"}
+ARGS=${ARGS:-"--full --steps 10 --warmup 3 --no-cpu-baseline --rollout-T 100 --c2-envs 0 --c5-envs 0 --no-ea-line"}
 timeout -k 10 400 rocprofv3 --kernel-trace -d gpurun_out/trace_roll -o trace --output-format csv -- python bench.py $ARGS > gpurun_out/trace_roll_bench.log 2>&1 || exit $?
 f=$(find gpurun_out/trace_roll -name '*kernel_trace.csv' | head -1)
 python3 - "$f" > gpurun_out/trace_roll_summary.txt <<'PY'

@@ -437,6 +437,34 @@ def test_bench_window_accounting():
     assert m["ahead_change_steps"] == round((64 * 100 + 32 * 20 - 96 * 50) / 96, 1)
 
 
+def test_bench_output_snapshot_is_a_fixed_sample_within_budget(tmp_path):
+    """bench.snapshot_outputs / write_outputs (--dump-outputs): float arrays of what a step returned;
+    over the byte budget every array keeps the same seeded, sorted sample of envs, run after run."""
+    import torch
+    sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
+    import bench
+
+    E, W, L = 40000, 8, 34  # 2,220 B per env: over the 64 MB budget, so 28,828 envs are kept
+    g = torch.Generator().manual_seed(0)
+    res = (torch.rand((E, W, L), generator=g), torch.rand((E, W), generator=g),
+           (torch.rand(E, generator=g) < 0.5).to(torch.uint8), torch.rand((E, W, L), generator=g))
+    a, b = bench.snapshot_outputs(res), bench.snapshot_outputs(res)
+    assert sorted(a) == ["env_ids", "final_obs", "obs", "rewards", "truncated"]
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    ids = a["env_ids"].astype(np.int64)
+    n = bench.DUMP_BUDGET_BYTES // ((2 * W * L + W + 1) * 4 + 8)
+    assert len(ids) == n < E and np.all(np.diff(ids) > 0) and ids[-1] < E
+    assert sum(v.nbytes for v in a.values()) <= bench.DUMP_BUDGET_BYTES
+    for k, t in zip(("obs", "rewards", "truncated", "final_obs"), res):
+        assert a[k].dtype == np.float32 and np.array_equal(a[k], t.numpy()[ids].astype(np.float32))
+    # under the budget: every env, in order; a step without final observations leaves that array out
+    small = bench.snapshot_outputs(tuple(t[:100] for t in res[:3]) + (None,))
+    assert "final_obs" not in small and np.array_equal(small["env_ids"], np.arange(100.0))
+    bench.write_outputs(str(tmp_path / "dump"), small)
+    assert sorted(p.name for p in (tmp_path / "dump").iterdir()) == ["env_ids.npy", "obs.npy", "rewards.npy", "truncated.npy"]
+    assert np.array_equal(np.load(tmp_path / "dump" / "obs.npy"), res[0][:100].numpy())
+
+
 def test_dist_shard_partitions(monkeypatch):
     """marlsc.dist.shard: weak and strong env-id partitions (bench.py, BASELINE configs[2] / [3]); the
     episode-ahead budget split between ranks that share one card."""
