@@ -416,6 +416,52 @@ int msc_mlp2_relu_forward_sampled(const float* x, int64_t n_rows, int32_t in_dim
                                   const float* pre1, int32_t pre1_group, const msc_gaussian_epilogue* sample,
                                   msc_stream_t stream);
 
+/* Rollout inference of a mu / sigma-head actor (use_mu_sigma_head): replaces the torch layer sequence
+ * backbone -> MuSigmaHead.forward (architectures/mu_sigma_head.py:52-82, wired in
+ * rlmodules/base.py:434-435) and, with the sampling buffers, the EnvRunner's TorchDiagGaussian
+ * sample (rlmodules/base.py:480-557), by one launch. The backbone is MLPArchitecture.build with
+ * output_dim = hidden[-1] and no output activation; its last Linear is followed by the two Linear
+ * heads with no nonlinearity in between, so the caller folds them (marlsc/mlp.py:fold_head, in f64,
+ * rounded once): W_eff = [W_mu; W_sigma] W_out ([2k][hidden]), b_eff = [W_mu; W_sigma] b_out +
+ * [b_mu; b_sigma]. Per row: o = W_eff relu(.. hidden layers ..) + b_eff,
+ *   mu = act_mu(o[0..k)), log_std = clamp(act_sigma(o[k..2k)), log_std_min, log_std_max)
+ * (the mean is not clamped); dist_out [n_rows][2k] = [mu || log_std] when non-NULL; when eps is
+ * non-NULL, actions / logp / clipped as msc_gaussian_sample(mu, log_std with one row per row, floor
+ * log_std_min) computes them, operation for operation (bit-identical to that two-launch sequence).
+ * k <= 8 (9..16: msc_mlp{2,3}_relu_forward on W_eff with out_dim = 2k, then msc_gaussian_sample).
+ * w1p / w2p / b1 / b2 / pre1 / pre1_group as msc_mlp3_relu_forward's; bh = b_eff [2k];
+ * whp [hidden/2][2][stride] floats, the dual-head VALU layout msc_mlp_musigma_layout reports:
+ *   whp[s][h][c] = W_eff[c < stride/2 ? c : k + c - stride/2][32 (s / 16) + rho(s % 16, h)],
+ *   rho(r, h) = (r & 3) + 8 (r >> 2) + 4 h, zero where the head's column (c mod stride/2) >= k.
+ * msc_mlp_musigma_layout(hidden1, hidden2 (0: one hidden layer), k, &width, &stride): 0 and the
+ * per-head register width / stride, or an error when there is no dual-head kernel: k outside 1..8,
+ * unsupported hidden sizes (one hidden layer: up to 1024 units for k <= 4, 512 above), the MFMA
+ * output layer forced (MSC_MLP_V3=0), or a [256, 256] A/B form without a head variant
+ * (MSC_MLP_P8 = 4 / 2). */
+#define MSC_ACT_NONE 0
+#define MSC_ACT_RELU 1
+#define MSC_ACT_TANH 2
+#define MSC_ACT_ELU 3
+#define MSC_ACT_GELU 4 /* erf form */
+#define MSC_ACT_SIGMOID 5
+typedef struct msc_musigma_epilogue {
+  int32_t act_mu, act_sigma;       /* MSC_ACT_* */
+  float log_std_min, log_std_max;  /* MuSigmaHead.LOG_STD_MIN / LOG_STD_MAX: -4.6, 4.6 */
+  const float* eps;                /* [n_rows][k] standard-normal draws; NULL: no sampling */
+  float* actions;                  /* [n_rows][k]  (all three non-NULL exactly when eps is) */
+  float* logp;                     /* [n_rows] */
+  float* clipped;                  /* [n_rows][k] */
+  float* dist_out;                 /* [n_rows][2k] = [mu || log_std], or NULL */
+} msc_musigma_epilogue;
+int msc_mlp_musigma_layout(int32_t hidden1, int32_t hidden2, int32_t k, int32_t* width, int32_t* stride);
+int msc_mlp3_relu_musigma(const float* x, int64_t n_rows, int32_t in_dim, int32_t hidden1, int32_t hidden2, int32_t k,
+                          const float* w1p, const float* b1, const float* w2p, const float* b2, const float* whp,
+                          const float* bh, const float* pre1, int32_t pre1_group, const msc_musigma_epilogue* head,
+                          msc_stream_t stream);
+int msc_mlp2_relu_musigma(const float* x, int64_t n_rows, int32_t in_dim, int32_t hidden, int32_t k, const float* w1p,
+                          const float* b1, const float* whp, const float* bh, const float* pre1, int32_t pre1_group,
+                          const msc_musigma_epilogue* head, msc_stream_t stream);
+
 /* Utility: numpy's Generator.poisson on the device (synchronous; the env's own sampler, exposed for
  * known-answer tests): n draws with the rates lam_host[i % n_lam] (random_poisson: multiplication
  * method below 10, PTRS at or above, numpy/random/src/distributions/distributions.c) from the PCG64

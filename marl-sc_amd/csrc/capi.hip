@@ -1503,6 +1503,75 @@ int msc_mlp2_relu_forward_sampled(const float* x, int64_t n_rows, int32_t in_dim
   return mlp2_impl(x, n_rows, in_dim, hidden, out_dim, w1p, b1, w3p, b3, out, pre1, pre1_group, sample, stream);
 }
 
+// mu / sigma-head actors (replaces backbone -> MuSigmaHead.forward, mu_sigma_head.py:52-82, wired in
+// rlmodules/base.py:434-435, and the sampling of rlmodules/base.py:480-557)
+int msc_mlp_musigma_layout(int32_t hidden1, int32_t hidden2, int32_t k, int32_t* width, int32_t* stride) {
+  if (!width || !stride) return set_err(-1, "null argument");
+  if (k < 1 || k > 8) return set_err(-1, "k %d: the fused mu/sigma head supports 1..8 actions", k);
+  const int vk = mlp_head_width(k);
+  if (vk == 0) return set_err(-1, "the fused mu/sigma head needs the VALU output layer (MFMA layout forced: it cannot sample)");
+  if (hidden2 == 0) {
+    if (!mlp2_head_supported(hidden1, vk))
+      return set_err(-1, "hidden size %d: the fused mu/sigma head supports multiples of 32 up to %d for k = %d", hidden1,
+                     vk <= 4 ? 1024 : 512, k);
+  } else if (!mlp3_head_supported(hidden1, hidden2)) {
+    return set_err(-1, "hidden sizes %d, %d: no fused mu/sigma head (H1, H2 in {64, 128, 256, 512}; not the "
+                   "MSC_MLP_P8 = 4 / 2 forms of [256, 256])", hidden1, hidden2);
+  }
+  *width = vk;
+  *stride = mlp_head_stride(vk);
+  return 0;
+}
+
+static int musigma_args(const msc_musigma_epilogue* g, int32_t hidden1, int32_t hidden2, int32_t k, MlpMuSigma* ep) {
+  if (!g) return set_err(-1, "null argument");
+  int32_t vk, stride;
+  if (const int r = msc_mlp_musigma_layout(hidden1, hidden2, k, &vk, &stride)) return r;
+  auto act_ok = [](int a) { return a >= MSC_ACT_NONE && a <= MSC_ACT_SIGMOID; };
+  if (!act_ok(g->act_mu) || !act_ok(g->act_sigma))
+    return set_err(-1, "activation codes %d, %d: must be MSC_ACT_* (0..5)", g->act_mu, g->act_sigma);
+  if (!(g->log_std_min <= g->log_std_max)) return set_err(-1, "log_std_min must be <= log_std_max");
+  const bool any_out = g->actions || g->logp || g->clipped;
+  if (!g->eps && any_out) return set_err(-1, "sampling outputs given without eps");
+  if (g->eps && !(g->actions && g->logp && g->clipped)) return set_err(-1, "null sampling buffer");
+  if (!g->eps && !g->dist_out) return set_err(-1, "nothing to write: neither dist_out nor sampling buffers");
+  *ep = MlpMuSigma{g->act_mu, g->act_sigma, g->log_std_min, g->log_std_max, g->eps, g->actions, g->logp, g->clipped,
+                   g->dist_out};
+  return 0;
+}
+
+int msc_mlp3_relu_musigma(const float* x, int64_t n_rows, int32_t in_dim, int32_t hidden1, int32_t hidden2, int32_t k,
+                          const float* w1p, const float* b1, const float* w2p, const float* b2, const float* whp,
+                          const float* bh, const float* pre1, int32_t pre1_group, const msc_musigma_epilogue* head,
+                          msc_stream_t stream) {
+  if (pre1 && pre1_group < 1) return set_err(-1, "pre1_group %d must be >= 1", pre1_group);
+  if (((uintptr_t)b1 | (uintptr_t)b2 | (uintptr_t)pre1 | (uintptr_t)w1p | (uintptr_t)w2p | (uintptr_t)whp) & 15)
+    return set_err(-1, "b1, b2, pre1 and the packed weights must be 16-byte aligned");
+  if (!x || !w1p || !b1 || !w2p || !b2 || !whp || !bh) return set_err(-1, "null argument");
+  if (n_rows < 0 || in_dim < 1 || in_dim > 1024) return set_err(-1, "bad shape (n_rows %lld, in_dim %d)", (long long)n_rows, in_dim);
+  if (hidden2 == 0) return set_err(-1, "hidden2 must be one of {64, 128, 256, 512} (one hidden layer: msc_mlp2_relu_musigma)");
+  MlpMuSigma ep{};
+  if (const int r = musigma_args(head, hidden1, hidden2, k, &ep)) return r;
+  HIP_TRY(launch_mlp3_musigma(x, n_rows, in_dim, hidden1, hidden2, k, w1p, b1, w2p, b2, whp, bh, pre1,
+                              pre1 ? pre1_group : 1, (hipStream_t)stream, ep));
+  return 0;
+}
+
+int msc_mlp2_relu_musigma(const float* x, int64_t n_rows, int32_t in_dim, int32_t hidden, int32_t k, const float* w1p,
+                          const float* b1, const float* whp, const float* bh, const float* pre1, int32_t pre1_group,
+                          const msc_musigma_epilogue* head, msc_stream_t stream) {
+  if (pre1 && pre1_group < 1) return set_err(-1, "pre1_group %d must be >= 1", pre1_group);
+  if (((uintptr_t)b1 | (uintptr_t)pre1 | (uintptr_t)w1p | (uintptr_t)whp) & 15)
+    return set_err(-1, "b1, pre1 and the packed weights must be 16-byte aligned");
+  if (!x || !w1p || !b1 || !whp || !bh) return set_err(-1, "null argument");
+  if (n_rows < 0 || in_dim < 1 || in_dim > 1024) return set_err(-1, "bad shape (n_rows %lld, in_dim %d)", (long long)n_rows, in_dim);
+  MlpMuSigma ep{};
+  if (const int r = musigma_args(head, hidden, 0, k, &ep)) return r;
+  HIP_TRY(launch_mlp2_musigma(x, n_rows, in_dim, hidden, k, w1p, b1, whp, bh, pre1, pre1 ? pre1_group : 1,
+                              (hipStream_t)stream, ep));
+  return 0;
+}
+
 int msc_adv_normalize_grouped(float* adv, int64_t n, int32_t n_groups, const double* stats, msc_stream_t stream) {
   if (!adv || !stats || n < 0) return set_err(-1, "bad argument");
   if (n_groups < 1 || n_groups > 64 || n % n_groups != 0)

@@ -255,6 +255,31 @@ hipError_t launch_mlp2_relu(const float* x, int64_t n, int L, int H1, int KO, co
                             const float* w3p, const float* b3, float* out, const float* pre1, int grp, hipStream_t st,
                             const MlpSample* smp = nullptr);
 bool mlp2_supported(int H1);
+int mlp_p8();    // MSC_MLP_P8: the A/B form of the [256, 256] kernel (mlp.hip)
+int mlp_prio();  // MSC_MLP_PRIO
+// the fused MLPs' mu / sigma head epilogue (msc_musigma_epilogue): activations (MSC_ACT_* codes), the
+// log_std clamp, the optional store of [mu || log_std] and the optional sampling (act == nullptr: none)
+struct MlpMuSigma {
+  int act_mu, act_sigma;
+  float lo, hi;
+  const float* eps;  // [n][K]
+  float* act;        // [n][K]
+  float* logp;       // [n]
+  float* clipped;    // [n][K]
+  float* dist;       // [n][2 K]
+};
+// per-head sums of the dual-head VALU output layer for K actions (0: none), and the floats the packed
+// weights hold per (hidden pair, lane half): the mu weights in the first half, sigma's in the second
+int mlp_head_width(int K);
+inline int mlp_head_stride(int width) { return width <= 4 ? 8 : 16; }
+bool mlp3_head_supported(int H1, int H2);
+bool mlp2_head_supported(int H1, int width);
+hipError_t launch_mlp3_musigma(const float* x, int64_t n, int L, int H1, int H2, int K, const float* w1p, const float* b1,
+                               const float* w2p, const float* b2, const float* whp, const float* bh, const float* pre1,
+                               int grp, hipStream_t st, const MlpMuSigma& ep);
+hipError_t launch_mlp2_musigma(const float* x, int64_t n, int L, int H1, int K, const float* w1p, const float* b1,
+                               const float* whp, const float* bh, const float* pre1, int grp, hipStream_t st,
+                               const MlpMuSigma& ep);
 hipError_t launch_normal_keyed(float* out, int32_t n_steps, int64_t n_rows, int32_t row_len, int64_t row0,
                                uint64_t seed, uint64_t step0, hipStream_t st);
 hipError_t launch_meanstd_filter(const float* x, float* out, int64_t E, int32_t C, const uint8_t* mask, int32_t update,

@@ -85,6 +85,13 @@ class MscGaussianEpilogue(C.Structure):
                 ("eps", C.c_void_p), ("actions", C.c_void_p), ("logp", C.c_void_p), ("clipped", C.c_void_p)]
 
 
+class MscMuSigmaEpilogue(C.Structure):
+    """msc_musigma_epilogue (include/marlsc.h): the fused MLPs' mu / sigma-head epilogue."""
+    _fields_ = [("act_mu", C.c_int32), ("act_sigma", C.c_int32), ("log_std_min", C.c_float),
+                ("log_std_max", C.c_float), ("eps", C.c_void_p), ("actions", C.c_void_p), ("logp", C.c_void_p),
+                ("clipped", C.c_void_p), ("dist_out", C.c_void_p)]
+
+
 def lib() -> C.CDLL:
     """Load libmarlsc.so (built by __graft_entry__.build()). Raises if it is missing."""
     global _LIB
@@ -141,6 +148,11 @@ def lib() -> C.CDLL:
                                                 vp, vp, vp, vp, vp, C.c_int32, P(MscGaussianEpilogue), vp]
     L.msc_mlp2_relu_forward_sampled.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp,
                                                 vp, C.c_int32, P(MscGaussianEpilogue), vp]
+    L.msc_mlp_musigma_layout.argtypes = [C.c_int32, C.c_int32, C.c_int32, ip, ip]
+    L.msc_mlp3_relu_musigma.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp,
+                                        vp, vp, C.c_int32, P(MscMuSigmaEpilogue), vp]
+    L.msc_mlp2_relu_musigma.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, C.c_int32,
+                                        P(MscMuSigmaEpilogue), vp]
     L.msc_meanstd_scratch_doubles.argtypes = [C.c_int64, C.c_int32]
     L.msc_meanstd_scratch_doubles.restype = C.c_int64
     L.msc_meanstd_filter.argtypes = [vp, vp, C.c_int64, C.c_int32, vp, C.c_int32, vp, vp, C.c_double, C.c_double, vp]
@@ -165,5 +177,6 @@ EXPORTED_SYMBOLS = [
     "msc_env_read_state", "msc_env_state_bytes", "msc_env_save_state", "msc_env_load_state", "msc_env_check",
     "msc_env_set_episode_counters", "msc_gae", "msc_adv_normalize", "msc_gae_grouped", "msc_adv_normalize_grouped", "msc_gaussian_sample", "msc_mlp3_w3_layout", "msc_mlp3_relu_forward", "msc_mlp2_relu_forward",
     "msc_mlp3_relu_forward_sampled", "msc_mlp2_relu_forward_sampled",
+    "msc_mlp_musigma_layout", "msc_mlp3_relu_musigma", "msc_mlp2_relu_musigma",
     "msc_normal_keyed", "msc_poisson_draws", "msc_meanstd_scratch_doubles", "msc_meanstd_filter", "msc_seedseq_u32", "msc_last_error", "msc_abi_version",
 ]

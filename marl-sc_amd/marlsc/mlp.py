@@ -14,6 +14,10 @@ torch [out, in] matrices (index maps cached per shape, packs cached per weight v
 learner's updates are picked up and the pack is rebuilt at most once per optimizer step). A pack
 built on one HIP stream and used on another is ordered by an event (rollout lanes).
 
+Actors with the reference's mu/sigma head (`use_mu_sigma_head`) run through the same kernels with a
+dual-head output layer (msc_mlp{2,3}_relu_musigma, csrc/mlp_musigma.hip): see the section at the
+end of this file.
+
 There is no CPU fallback: a CUDA tensor on a build without libmarlsc raises (abi.lib()).
 """
 from __future__ import annotations
@@ -107,10 +111,11 @@ def pack_mlp3(w1: torch.Tensor, w2: Optional[torch.Tensor], w3: torch.Tensor, la
     return w1p.contiguous(), w2p, w3p.contiguous()
 
 
-def fused_layers(mods) -> int:
+def fused_layers(mods, max_out: int = MAX_OUT) -> int:
     """2 or 3 when mods (Linear, ReLU, ..., Linear) has a fused kernel: one hidden layer of a
-    multiple of 32 up to 1024 units, or two of {64, 128, 256, 512}; <= 1024 inputs, <= 32 outputs.
-    0 otherwise (the caller runs the torch layers)."""
+    multiple of 32 up to 1024 units, or two of {64, 128, 256, 512}; <= 1024 inputs, <= 32 outputs
+    (max_out: the bound on the last Linear, wider for a backbone whose last Linear is folded into
+    the mu/sigma head). 0 otherwise (the caller runs the torch layers)."""
     n = len(mods)
     if n not in (3, 5):
         return 0
@@ -122,7 +127,7 @@ def fused_layers(mods) -> int:
     for a, b in zip(lins[:-1], lins[1:]):
         if b.in_features != a.out_features:
             return 0
-    if lins[0].in_features > MAX_IN or lins[-1].out_features > MAX_OUT:
+    if lins[0].in_features > MAX_IN or lins[-1].out_features > max_out:
         return 0
     if n == 3:
         H = lins[0].out_features
@@ -139,6 +144,31 @@ class _Pack:
 
     def __init__(self):
         self.key, self.tensors, self.stream, self.event = None, None, None, None
+
+
+def _cached_pack(l1: nn.Module, slot, weights, cur, build):
+    """The head actors' pack cached on the first Linear under `slot`, by mlp3_forward's rules: rebuilt
+    by build() when any of `weights` changed (version counters) or moved; ordered after its packing
+    kernels on another stream."""
+    packs = getattr(l1, "_msc_packs", None)
+    if packs is None:
+        packs = l1._msc_packs = {}
+    pk = packs.setdefault(slot, _Pack())
+    key = tuple((p.data_ptr(), p._version) for p in weights)
+    if pk.key != key:
+        pk.tensors = build()
+        pk.key = key
+        pk.stream = cur
+        pk.event = torch.cuda.Event()
+        pk.event.record(cur)
+    elif pk.stream != cur:
+        # packed on another stream (e.g. the main stream of a multi-lane rollout): order this
+        # stream after the packing kernels, and keep the pack's memory alive for this stream's use
+        cur.wait_event(pk.event)
+        for t in pk.tensors:
+            if t is not None:
+                t.record_stream(cur)
+    return pk.tensors
 
 
 def sample_fusable(mods) -> bool:
@@ -227,3 +257,197 @@ def mlp3_forward(mods, x: torch.Tensor, out: Optional[torch.Tensor] = None, *, w
         abi.check(abi.lib().msc_mlp3_relu_forward(vp(xf), n, L, l1.out_features, l2.out_features, KO, vp(w1p), vp(b1),
                                                   vp(w2p), vp(b2), vp(w3p), vp(b3), vp(out), vp(pre1), int(group), st))
     return out.reshape(*lead, KO)
+
+
+# ----------------------------------------------------------------------------------------------
+# mu/sigma-head actors (use_mu_sigma_head): backbone Linear-ReLU(-Linear-ReLU)-Linear, then two
+# Linear heads with no nonlinearity in between. For inference the backbone's last Linear is folded
+# into the heads: W_eff = [W_mu; W_sigma] W_out ([2K, H]), b_eff = [W_mu; W_sigma] b_out +
+# [b_mu; b_sigma], computed in f64 and rounded once to f32, so a head actor costs the MFMA work of
+# a plain actor with 2K outputs.
+# ----------------------------------------------------------------------------------------------
+HEAD_MAX_FUSED = 8     # K of msc_mlp{2,3}_relu_musigma (VALU dual-head output layer)
+HEAD_MAX_FOLDED = 16   # 2K <= 32: the plain fused MLP on the folded weights (MFMA output layer)
+_ACT_CODE = {type(None): 0, nn.ReLU: 1, nn.Tanh: 2, nn.ELU: 3, nn.GELU: 4, nn.Sigmoid: 5}  # MSC_ACT_*
+
+
+def fold_head(out_lin: nn.Linear, head):
+    """(W_eff [2K, H], b_eff [2K]) f32: `out_lin` folded into head.mu_head / head.sigma_head."""
+    wh = torch.cat([head.mu_head.weight, head.sigma_head.weight]).detach().double()
+    bh = torch.cat([head.mu_head.bias, head.sigma_head.bias]).detach().double()
+    w = wh @ out_lin.weight.detach().double()
+    b = wh @ out_lin.bias.detach().double() + bh
+    return w.float().contiguous(), b.float().contiguous()
+
+
+def musigma_layout(H1: int, H2: int, K: int):
+    """msc_mlp_musigma_layout: (per-head width, floats per (hidden pair, lane half)) of the packed
+    dual-head weights for hidden sizes [H1, H2] (H2 = 0: one hidden layer) and K actions; None when
+    the library has no fused head kernel for them."""
+    w, s = C.c_int32(0), C.c_int32(0)
+    if abi.lib().msc_mlp_musigma_layout(int(H1), int(H2), int(K), C.byref(w), C.byref(s)) != 0:
+        return None
+    return w.value, s.value
+
+
+def _head_ok(mods, head) -> int:
+    """fused_layers of a head actor's backbone (its last Linear is folded: any width), 0 when the
+    head does not sit on it as the reference builds it."""
+    nl = fused_layers(mods, max_out=MAX_HIDDEN_1)
+    if nl == 0 or type(head.mu_activation) not in _ACT_CODE or type(head.sigma_activation) not in _ACT_CODE:
+        return 0
+    H, K = mods[-1].out_features, head.mu_head.out_features
+    if head.mu_head.in_features != H or head.sigma_head.in_features != H or head.sigma_head.out_features != K \
+            or mods[-1].in_features != H or head.mu_head.bias is None or head.sigma_head.bias is None:
+        return 0
+    return nl
+
+
+def musigma_tier(mods, head) -> int:
+    """Inference path of a head actor (backbone mods, MuSigmaHead): 1 = one fused launch
+    (musigma_forward), 2 = folded weights through the plain fused MLP (musigma_folded), 3 = torch
+    layers."""
+    nl = _head_ok(mods, head)
+    if nl == 0:
+        return 3
+    K = head.mu_head.out_features
+    if K <= HEAD_MAX_FUSED:
+        H2 = mods[2].out_features if nl == 3 else 0
+        return 1 if musigma_layout(mods[0].out_features, H2, K) is not None else 3
+    return 2 if K <= HEAD_MAX_FOLDED else 3
+
+
+def _head_index(H: int, K: int, stride: int, device):
+    """whp[s][h][c] = W_eff[c < stride / 2 ? c : K + c - stride / 2][32 (s // 16) + rho(s % 16, h)]
+    (0 where the head's column index is >= K): mu weights in the first half, sigma's in the second."""
+    key = ("head", H, K, stride, str(device))
+    if key not in _IDX:
+        sv = torch.arange((H // 32) * 16, device=device)[:, None, None]
+        hv = torch.arange(2, device=device)[None, :, None]
+        cv = torch.arange(stride, device=device)[None, None, :]
+        a = cv % (stride // 2)
+        row = a.clamp(max=K - 1) + K * (cv // (stride // 2))
+        idx = (row * H + (sv // 16) * 32 + _rho(sv % 16, hv)).reshape(-1)
+        _IDX[key] = (idx, (a < K).expand((H // 32) * 16, 2, stride).reshape(-1))
+    return _IDX[key]
+
+
+def _head_pack(mods, head, nl: int, w1: torch.Tensor, cur, fused: bool):
+    """(w1p, w2p, whp, b_eff) of the folded head actor: whp in the dual-head VALU layout (fused) or
+    the MFMA fragments of the 2K-row folded matrix. The cache key holds every contributing tensor,
+    biases included (they enter b_eff)."""
+    l1, lo = mods[0], mods[-1]
+    l2 = mods[2] if nl == 3 else None
+    hs = (lo.weight, lo.bias, head.mu_head.weight, head.mu_head.bias, head.sigma_head.weight, head.sigma_head.bias)
+    weights = ((w1,) if l2 is None else (w1, l2.weight)) + hs
+
+    def build():
+        w_eff, b_eff = fold_head(lo, head)
+        w1p, w2p, w3p = pack_mlp3(w1, None if l2 is None else l2.weight, w_eff, layout=0)
+        if fused:
+            H, K = lo.out_features, head.mu_head.out_features
+            _, stride = musigma_layout(l1.out_features, l2.out_features if l2 is not None else 0, K)
+            idx, valid = _head_index(H, K, stride, w1.device)
+            w3p = torch.where(valid, w_eff.reshape(-1)[idx], torch.zeros((), device=w1.device)).contiguous()
+        return w1p, w2p, w3p, b_eff
+
+    slot = ("musigma" if fused else "musigma_folded", w1.shape, w1.stride(), w1.storage_offset())
+    return _cached_pack(l1, slot, weights, cur, build)
+
+
+def _rows(x: torch.Tensor, L: int) -> torch.Tensor:
+    xf = x.reshape(-1, L)
+    if xf.dtype != torch.float32 or not xf.is_contiguous():
+        xf = xf.float().contiguous()
+    return xf
+
+
+def musigma_forward(mods, head, x: torch.Tensor, dist_out: Optional[torch.Tensor] = None, *, sample=None,
+                    w1: Optional[torch.Tensor] = None, pre1: Optional[torch.Tensor] = None, group: int = 1):
+    """msc_mlp{2,3}_relu_musigma over x [..., L] (f32 CUDA): backbone -> folded dual head -> head
+    activations and the log_std clamp in one launch (musigma_tier(mods, head) must be 1).
+    sample: (eps, actions, logp, clipped) -- msc_gaussian_sample's arithmetic on each row's
+    (mu, log_std) while they are in registers; the distribution inputs [mu || log_std] ([..., 2K])
+    then go to `dist_out` only when it is given. Without `sample` they are always written (to a new
+    buffer when dist_out is None). w1 / pre1 / group as in mlp3_forward. Returns dist_out or None."""
+    nl = _head_ok(mods, head)
+    K = head.mu_head.out_features
+    if musigma_tier(mods, head) != 1:
+        raise ValueError("no fused mu/sigma-head kernel for this actor (see musigma_tier)")
+    l1 = mods[0]
+    l2 = mods[2] if nl == 3 else None
+    w1 = l1.weight if w1 is None else w1
+    L = w1.shape[1]
+    if x.shape[-1] != L:
+        raise ValueError(f"input has {x.shape[-1]} features, the MLP expects {L}")
+    cur = torch.cuda.current_stream(x.device)
+    w1p, w2p, whp, b_eff = _head_pack(mods, head, nl, w1, cur, True)
+    lead, xf = x.shape[:-1], _rows(x, L)
+    n = xf.shape[0]
+    if pre1 is not None:
+        pre1 = pre1.float().contiguous()
+        if group < 1 or n % group or pre1.shape != (n // group, l1.out_features):
+            raise ValueError(f"pre1 must be [{n // max(group, 1)}, {l1.out_features}] for {n} rows in groups of {group}")
+    if sample is None and dist_out is None:
+        dist_out = torch.empty((n, 2 * K), device=x.device, dtype=torch.float32)
+    if dist_out is not None and not (dist_out.is_cuda and dist_out.dtype == torch.float32
+                                     and dist_out.is_contiguous() and dist_out.numel() == n * 2 * K):
+        raise ValueError("dist_out must be a contiguous float32 CUDA tensor of rows x 2K")
+    vp = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+    eps = act = logp = clipped = None
+    if sample is not None:
+        eps, act, logp, clipped = sample
+        for t in sample:
+            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+                raise ValueError("sampling buffers must be contiguous float32 CUDA tensors")
+        if eps.numel() != n * K or act.numel() != n * K or clipped.numel() != n * K or logp.numel() != n:
+            raise ValueError("sampling buffers do not match the MLP's rows / actions")
+    from .rollout import LOG_STD_MAX, LOG_STD_MIN
+    ep = abi.MscMuSigmaEpilogue(_ACT_CODE[type(head.mu_activation)], _ACT_CODE[type(head.sigma_activation)],
+                                C.c_float(LOG_STD_MIN), C.c_float(LOG_STD_MAX), vp(eps), vp(act), vp(logp),
+                                vp(clipped), vp(dist_out))
+    st = C.c_void_p(cur.cuda_stream)
+    b1 = l1.bias.detach().float().contiguous()
+    if l2 is None:
+        abi.check(abi.lib().msc_mlp2_relu_musigma(vp(xf), n, L, l1.out_features, K, vp(w1p), vp(b1), vp(whp), vp(b_eff),
+                                                  vp(pre1), int(group), C.byref(ep), st))
+    else:
+        b2 = l2.bias.detach().float().contiguous()
+        abi.check(abi.lib().msc_mlp3_relu_musigma(vp(xf), n, L, l1.out_features, l2.out_features, K, vp(w1p), vp(b1),
+                                                  vp(w2p), vp(b2), vp(whp), vp(b_eff), vp(pre1), int(group),
+                                                  C.byref(ep), st))
+    return None if dist_out is None else dist_out.reshape(*lead, 2 * K)
+
+
+def musigma_folded(mods, head, x: torch.Tensor):
+    """(mu, log_std) [..., K] of a head actor with up to 16 actions: msc_mlp{2,3}_relu_forward on the
+    folded weights (2K <= 32 rows of the MFMA output layer), head activations and clamp in torch."""
+    nl = _head_ok(mods, head)
+    K = head.mu_head.out_features
+    if nl == 0 or K > HEAD_MAX_FOLDED:
+        raise ValueError("no folded mu/sigma-head path for this actor (see musigma_tier)")
+    l1 = mods[0]
+    l2 = mods[2] if nl == 3 else None
+    L = l1.in_features
+    cur = torch.cuda.current_stream(x.device)
+    w1p, w2p, w3p, b_eff = _head_pack(mods, head, nl, l1.weight, cur, False)
+    lead, xf = x.shape[:-1], _rows(x, L)
+    n = xf.shape[0]
+    out = torch.empty((n, 2 * K), device=x.device, dtype=torch.float32)
+    vp = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+    st = C.c_void_p(cur.cuda_stream)
+    b1 = l1.bias.detach().float().contiguous()
+    if l2 is None:
+        abi.check(abi.lib().msc_mlp2_relu_forward(vp(xf), n, L, l1.out_features, 2 * K, vp(w1p), vp(b1), vp(w3p),
+                                                  vp(b_eff), vp(out), None, 1, st))
+    else:
+        b2 = l2.bias.detach().float().contiguous()
+        abi.check(abi.lib().msc_mlp3_relu_forward(vp(xf), n, L, l1.out_features, l2.out_features, 2 * K, vp(w1p), vp(b1),
+                                                  vp(w2p), vp(b2), vp(w3p), vp(b_eff), vp(out), None, 1, st))
+    from .rollout import LOG_STD_MAX, LOG_STD_MIN
+    mu, ls = out[:, :K], out[:, K:]
+    if head.mu_activation is not None:
+        mu = head.mu_activation(mu)
+    if head.sigma_activation is not None:
+        ls = head.sigma_activation(ls)
+    return mu.reshape(*lead, K), torch.clamp(ls, LOG_STD_MIN, LOG_STD_MAX).reshape(*lead, K)

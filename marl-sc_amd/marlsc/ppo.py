@@ -51,7 +51,8 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from . import dist as mdist
-from .rollout import MLP, RolloutCollector, RolloutConfig, fused_actor_sample, mlp_forward, split_global_mlp
+from .rollout import (LOG_STD_MIN, MLP, RolloutCollector, RolloutConfig, build_actor, check_head_config,
+                      fused_actor_sample, gaussian_sample, head_sample, mlp_forward, split_global_mlp)
 
 LOG2PI = math.log(2 * math.pi)
 ENTROPY_CONST = 0.5 * math.log(2 * math.pi * math.e)
@@ -125,11 +126,12 @@ class PPOConfig:
         nets = self.networks or {}
         if nets.get("shared_layers"):
             raise ValueError("shared_layers (GRU) networks are outside this build's training path")
+        head = check_head_config(nets)
         return RolloutConfig(gamma=float(self.gamma), lam=float(self.lam) if self.use_gae else 1.0,
                              actor_obs_type=self.actor_obs_type, critic_obs_type=self.critic_obs_type,
                              logstd_init=float(self.logstd_init), logstd_floor=float(self.logstd_floor),
                              actor=(nets.get("actor") or {}).get("config"),
-                             critic=(nets.get("critic") or {}).get("config"))
+                             critic=(nets.get("critic") or {}).get("config"), use_mu_sigma_head=head)
 
     def lr_at(self, timestep: int) -> float:
         """RLlib learning-rate schedule: piecewise linear over [[t, lr], ...], constant outside."""
@@ -149,16 +151,25 @@ class PPOConfig:
 # modules: one shared policy or one per agent (the reference's policy mapping, mappo.py:102-113)
 # ----------------------------------------------------------------------------------------------
 class AgentModule(nn.Module):
-    """ActorCriticRLModule for MLP networks (rlmodules/base.py:480-715)."""
+    """ActorCriticRLModule for MLP networks (rlmodules/base.py:480-715). use_mu_sigma_head: the actor
+    is the backbone under `mu_sigma_head` and there is no `log_std` parameter (base.py:213-252)."""
 
     def __init__(self, local_obs_dim: int, global_obs_dim: int, action_dim: int, rc: RolloutConfig):
         super().__init__()
         full = local_obs_dim + global_obs_dim
-        self.actor = MLP(full if rc.actor_obs_type == "global" else local_obs_dim, action_dim,
-                         rc.actor or {"hidden_sizes": [256, 256]})
+        self.actor, head = build_actor(full if rc.actor_obs_type == "global" else local_obs_dim, action_dim, rc,
+                                       {"hidden_sizes": [256, 256]})
+        self.head_mode = head is not None
+        if self.head_mode:
+            self.mu_sigma_head = head
         self.critic = MLP(full if rc.critic_obs_type == "global" else local_obs_dim, 1,
                           rc.critic or {"hidden_sizes": [256, 256]})
-        self.log_std = nn.Parameter(torch.full((action_dim,), float(rc.logstd_init)))
+        if not self.head_mode:
+            self.log_std = nn.Parameter(torch.full((action_dim,), float(rc.logstd_init)))
+
+    def dist(self, x: torch.Tensor):
+        """Head mode: (mu, log_std) of the actor input x through the torch layers."""
+        return self.mu_sigma_head(self.actor(x))
 
 
 class MultiAgentActorCritic(nn.Module):
@@ -170,6 +181,7 @@ class MultiAgentActorCritic(nn.Module):
         self.rc, self.shared, self.W = rc, bool(shared), int(n_agents)
         self.policies = nn.ModuleList([AgentModule(local_obs_dim, global_obs_dim, action_dim, rc)
                                        for _ in range(1 if shared else n_agents)])
+        self.head_mode = bool(rc.use_mu_sigma_head)
 
     def _x(self, local_obs, full_obs, kind):
         return full_obs if kind == "global" else local_obs
@@ -180,11 +192,15 @@ class MultiAgentActorCritic(nn.Module):
         return torch.stack([fn(p, x[..., w, :]) for w, p in enumerate(self.policies)], dim=-2)
 
     def actor_mean(self, local_obs, full_obs=None):
+        if self.head_mode:
+            return self.dist_inputs(local_obs, full_obs)[0]
         return self._per_agent(lambda p, v: p.actor(v), self._x(local_obs, full_obs, self.rc.actor_obs_type))
 
-    def log_std_table(self) -> torch.Tensor:
+    def log_std_table(self) -> Optional[torch.Tensor]:
         """[P, K] unclamped log_std rows (P = 1 shared, W per agent) for msc_gaussian_sample, which
-        applies logstd_floor itself."""
+        applies logstd_floor itself. None with the mu/sigma head (per-row log_std: sample_actions)."""
+        if self.head_mode:
+            return None
         return torch.stack([p.log_std.detach().float() for p in self.policies]).contiguous()
 
     def actor_sample(self, local_obs, full_obs, sample) -> bool:
@@ -193,7 +209,22 @@ class MultiAgentActorCritic(nn.Module):
             return False
         return fused_actor_sample(self.policies[0].actor, self._x(local_obs, full_obs, self.rc.actor_obs_type), sample)
 
+    def sample_actions(self, local_obs, full_obs, eps, actions, logp) -> torch.Tensor:
+        """Head mode: one rollout step's actor forward and sampling. The shared policy takes the
+        fused paths of rollout.head_sample; per-agent policies run the torch layers."""
+        x = self._x(local_obs, full_obs, self.rc.actor_obs_type)
+        if self.shared:
+            return head_sample(self.policies[0].actor, self.policies[0].mu_sigma_head, x, eps, actions, logp)
+        mu, ls = self.dist_inputs(local_obs, full_obs)
+        return gaussian_sample(mu.contiguous(), ls.contiguous(), LOG_STD_MIN, eps, actions, logp)
+
     def dist_inputs(self, local_obs, full_obs=None):
+        if self.head_mode:  # (mu, log_std) per row through the torch layers
+            x = self._x(local_obs, full_obs, self.rc.actor_obs_type)
+            if self.shared:
+                return self.policies[0].dist(x)
+            d = [p.dist(x[..., w, :]) for w, p in enumerate(self.policies)]
+            return torch.stack([m for m, _ in d], dim=-2), torch.stack([s for _, s in d], dim=-2)
         floor = self.rc.logstd_floor
         mean = self.actor_mean(local_obs, full_obs)
         if self.shared:
@@ -332,8 +363,11 @@ class PPOLearner:
         full = None
         if rc.actor_obs_type == "global" or rc.critic_obs_type == "global":
             full = torch.cat([local, obs[torch.div(rows, W, rounding_mode="floor")].reshape(-1, W * L)], dim=-1)
-        mean = policy.actor(full if rc.actor_obs_type == "global" else local)
-        log_std = torch.clamp(policy.log_std, min=rc.logstd_floor).expand_as(mean)
+        if policy.head_mode:  # state-dependent log_std from the head, no free parameter
+            mean, log_std = policy.dist(full if rc.actor_obs_type == "global" else local)
+        else:
+            mean = policy.actor(full if rc.actor_obs_type == "global" else local)
+            log_std = torch.clamp(policy.log_std, min=rc.logstd_floor).expand_as(mean)
         values = policy.critic(full if rc.critic_obs_type == "global" else local).squeeze(-1)
         return mean, log_std, values
 
@@ -661,7 +695,8 @@ class PPOTrainer:
 
     def export_module_weights(self, path: Union[str, Path]) -> Path:
         """module_weights.pt: the state dict of the policy module agent 0 maps to (the shared policy,
-        or agent 0's own), keys actor.* / critic.* / log_std as the reference RLModule's
+        or agent 0's own), keys actor.* / critic.* / log_std (mu_sigma_head.* in place of log_std with
+        use_mu_sigma_head) as the reference RLModule's
         (src/utils/weight_transfer.py:15-33, runner.py:379-395)."""
         p = Path(path)
         p.parent.mkdir(parents=True, exist_ok=True)

@@ -9,6 +9,8 @@ unpinned against the reference and checked against the numpy GAE in oracle/gae_r
   (src/algorithms/models/rlmodules/base.py:480-715) for MLP networks without shared layers --
   actor on the local slice (or the full flat obs when actor_obs_type == "global"), free `log_std`
   clamped at `logstd_floor` (`_append_log_std`), critic on local (IPPO) or full flat obs (MAPPO);
+  with `use_mu_sigma_head` the actor is a backbone under `MuSigmaHead` (base.py:213-252, :434-435;
+  architectures/mu_sigma_head.py) and log_std depends on the observation (`head_sample`);
 * GAE(gamma, lambda) with truncation bootstrap V(final_obs) and RLlib's per-batch standardisation
   `(A - mean) / max(1e-4, std)`, statistics all-reduced across ranks (marlsc/dist.py).
 
@@ -53,6 +55,71 @@ class MLP(nn.Sequential):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         return mlp_forward(self, x)
+
+
+LOG_STD_MIN, LOG_STD_MAX = -4.6, 4.6  # MuSigmaHead.LOG_STD_MIN / LOG_STD_MAX (mu_sigma_head.py:22-23)
+
+
+class MuSigmaHead(nn.Module):
+    """The reference's state-dependent Gaussian head (architectures/mu_sigma_head.py:52-82, following
+    its code, not its docstring): on the backbone features f, mu = act_mu(mu_head(f)) -- not clamped
+    -- and log_std = clamp(act_sigma(sigma_head(f)), -4.6, 4.6). Returns (mu, log_std) instead of
+    their concatenation. action_low / action_high are the reference's buffers (unused by forward)."""
+
+    def __init__(self, backbone_dim: int, action_dim: int, output_activation_mu: Optional[str] = None,
+                 output_activation_sigma: Optional[str] = None):
+        super().__init__()
+        self.mu_head = nn.Linear(backbone_dim, action_dim)
+        self.sigma_head = nn.Linear(backbone_dim, action_dim)
+        self.register_buffer("action_low", torch.full((action_dim,), -1.0))
+        self.register_buffer("action_high", torch.full((action_dim,), 1.0))
+        self.mu_activation = _act(output_activation_mu) if output_activation_mu else None
+        self.sigma_activation = _act(output_activation_sigma) if output_activation_sigma else None
+
+    def forward(self, features: torch.Tensor):
+        mu = self.mu_head(features)
+        if self.mu_activation is not None:
+            mu = self.mu_activation(mu)
+        log_std = self.sigma_head(features)
+        if self.sigma_activation is not None:
+            log_std = self.sigma_activation(log_std)
+        return mu, torch.clamp(log_std, LOG_STD_MIN, LOG_STD_MAX)
+
+
+def check_head_config(nets: Dict[str, Any]) -> bool:
+    """ActorCriticConfig._validate_output_activations (config/schema.py:1066-1093) on a `networks`
+    dict, plus the head's need for an mlp actor (rlmodules/base.py:217-227 without the GRU);
+    returns use_mu_sigma_head."""
+    use = bool(nets.get("use_mu_sigma_head", False))
+    actor = nets.get("actor") or {}
+    acfg, ccfg = actor.get("config") or {}, (nets.get("critic") or {}).get("config") or {}
+    for k in ("output_activation_mu", "output_activation_sigma"):
+        if ccfg.get(k) is not None:
+            raise ValueError(f"{k} is only valid for the actor, not the critic")
+        if not use and acfg.get(k) is not None:
+            raise ValueError(f"{k} is only valid when use_mu_sigma_head is true")
+    if use:
+        if actor.get("type", "mlp") != "mlp":
+            raise ValueError(f"use_mu_sigma_head is not supported with actor type '{actor.get('type')}'")
+        if acfg.get("output_activation") is not None:
+            raise ValueError("output_activation must not be set on the actor when use_mu_sigma_head is true. "
+                             "Use output_activation_mu and/or output_activation_sigma instead.")
+    return use
+
+
+def build_actor(in_dim: int, action_dim: int, rc: "RolloutConfig", default: Dict[str, Any]):
+    """(actor, mu_sigma_head or None) as BaseRLModule builds them (rlmodules/base.py:213-262). With
+    the head the actor is the backbone: the hidden layers plus one Linear to hidden_sizes[-1]
+    features, every output_activation* key removed."""
+    cfg = rc.actor or default
+    if not rc.use_mu_sigma_head:
+        return MLP(in_dim, action_dim, cfg), None
+    cfg = dict(cfg)
+    act_mu, act_sigma = cfg.pop("output_activation_mu", None), cfg.pop("output_activation_sigma", None)
+    cfg.pop("output_activation", None)
+    hidden = cfg.get("hidden_sizes", [256])
+    dim = hidden[-1] if hidden else action_dim
+    return MLP(in_dim, dim, cfg), MuSigmaHead(dim, action_dim, act_mu, act_sigma)
 
 
 # Inference (no autograd): a whole Linear-ReLU-Linear-ReLU-Linear MLP with hidden sizes 64 / 128 /
@@ -104,6 +171,13 @@ class RolloutConfig:
     logstd_floor: float = -3.5
     actor: Optional[Dict[str, Any]] = None
     critic: Optional[Dict[str, Any]] = None
+    # networks.use_mu_sigma_head: the actor is a backbone under a MuSigmaHead (state-dependent
+    # log_std; no free log_std parameter, logstd_init / logstd_floor unused)
+    use_mu_sigma_head: bool = False
+
+    def __post_init__(self):
+        check_head_config({"use_mu_sigma_head": self.use_mu_sigma_head, "actor": {"config": self.actor},
+                           "critic": {"config": self.critic}})
 
     @classmethod
     def from_algorithm_config(cls, cfg: Dict[str, Any]) -> "RolloutConfig":
@@ -113,6 +187,7 @@ class RolloutConfig:
         nets = s.get("networks", {}) or {}
         if nets.get("shared_layers"):
             raise ValueError("shared_layers (GRU) networks are outside this build's rollout path")
+        head = check_head_config(nets)
         for k in ("actor", "critic"):
             if nets.get(k, {}).get("type", "mlp") != "mlp":
                 raise ValueError(f"{k}: only mlp networks are supported")
@@ -120,7 +195,8 @@ class RolloutConfig:
                    actor_obs_type=s.get("actor_obs_type", "local"),
                    critic_obs_type=s.get("critic_obs_type", "global" if a.get("name") == "mappo" else "local"),
                    logstd_init=float(s.get("logstd_init", -1.0)), logstd_floor=float(s.get("logstd_floor", -3.5)),
-                   actor=(nets.get("actor") or {}).get("config"), critic=(nets.get("critic") or {}).get("config"))
+                   actor=(nets.get("actor") or {}).get("config"), critic=(nets.get("critic") or {}).get("config"),
+                   use_mu_sigma_head=head)
 
 
 class ActorCritic(nn.Module):
@@ -128,24 +204,40 @@ class ActorCritic(nn.Module):
         super().__init__()
         self.local_obs_dim, self.rc = local_obs_dim, rc
         full = local_obs_dim + global_obs_dim
-        self.actor = MLP(full if rc.actor_obs_type == "global" else local_obs_dim, action_dim,
-                         rc.actor or {"hidden_sizes": [256, 256]})
+        self.actor, head = build_actor(full if rc.actor_obs_type == "global" else local_obs_dim, action_dim, rc,
+                                       {"hidden_sizes": [256, 256]})
+        self.head_mode = head is not None
+        if self.head_mode:
+            self.mu_sigma_head = head
         self.critic = MLP(full if rc.critic_obs_type == "global" else local_obs_dim, 1,
                           rc.critic or {"hidden_sizes": [64, 64]})
-        self.log_std = nn.Parameter(torch.full((action_dim,), float(rc.logstd_init)))
+        if not self.head_mode:
+            self.log_std = nn.Parameter(torch.full((action_dim,), float(rc.logstd_init)))
 
     def dist_inputs(self, local_obs: torch.Tensor, full_obs: Optional[torch.Tensor] = None):
         """(mean, log_std) -- ACTION_DIST_INPUTS split in two."""
+        if self.head_mode:  # the torch layer sequence (per-row log_std), with or without autograd
+            return self.mu_sigma_head(self.actor(full_obs if self.rc.actor_obs_type == "global" else local_obs))
         mean = self.actor_mean(local_obs, full_obs)
         log_std = torch.clamp(self.log_std, min=self.rc.logstd_floor).expand_as(mean)
         return mean, log_std
 
     def actor_mean(self, local_obs: torch.Tensor, full_obs: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if self.head_mode:
+            return self.dist_inputs(local_obs, full_obs)[0]
         return self.actor(full_obs if self.rc.actor_obs_type == "global" else local_obs)
 
-    def log_std_table(self) -> torch.Tensor:
-        """[1, K] unclamped log_std for msc_gaussian_sample (the kernel applies logstd_floor)."""
+    def log_std_table(self) -> Optional[torch.Tensor]:
+        """[1, K] unclamped log_std for msc_gaussian_sample (the kernel applies logstd_floor); None
+        with the mu/sigma head (log_std is per row: sample_actions)."""
+        if self.head_mode:
+            return None
         return self.log_std.detach().float().reshape(1, -1).contiguous()
+
+    def sample_actions(self, local_obs, full_obs, eps, actions, logp) -> torch.Tensor:
+        """Head mode: the rollout step's actor forward and sampling (see head_sample)."""
+        x = full_obs if self.rc.actor_obs_type == "global" else local_obs
+        return head_sample(self.actor, self.mu_sigma_head, x, eps, actions, logp)
 
     def actor_sample(self, local_obs: torch.Tensor, full_obs: Optional[torch.Tensor], sample) -> bool:
         """The actor forward with the action sampling fused into its kernel (see fused_actor_sample)."""
@@ -201,6 +293,27 @@ def fused_actor_sample(actor: nn.Sequential, x: torch.Tensor, sample) -> bool:
 
 def _vp(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def head_sample(actor: nn.Sequential, head: MuSigmaHead, x: torch.Tensor, eps: torch.Tensor, actions: torch.Tensor,
+                logp: torch.Tensor) -> torch.Tensor:
+    """One rollout step of a mu/sigma-head policy over x [..., in]: actions / logp written, the
+    [-1, 1] clipped actions returned. First path that applies (marlsc/mlp.py:musigma_tier):
+    1. K <= 8, fusable ReLU backbone: backbone -> folded dual head -> activations, clamp -> sampling
+       in one launch (msc_mlp{2,3}_relu_musigma);
+    2. 9 <= K <= 16: the fused MLP kernel on the folded weights (MFMA output layer), activations and
+       clamp in torch, msc_gaussian_sample with one log_std row per row;
+    3. otherwise the torch layers, then msc_gaussian_sample with one log_std row per row.
+    The sampling kernel's floor is the clamp's lower bound, so it changes nothing."""
+    tier = 3
+    if _FUSED and mlp3.ENABLED and x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled():
+        tier = mlp3.musigma_tier(list(actor), head)
+    if tier == 1:
+        clipped = torch.empty_like(actions)
+        mlp3.musigma_forward(list(actor), head, x, sample=(eps, actions, logp, clipped))
+        return clipped
+    mu, ls = mlp3.musigma_folded(list(actor), head, x) if tier == 2 else head(actor(x))
+    return gaussian_sample(mu.contiguous(), ls.contiguous(), LOG_STD_MIN, eps, actions, logp)
 
 
 def gaussian_sample(mean: torch.Tensor, log_std: torch.Tensor, logstd_floor: float, eps: torch.Tensor,
@@ -345,6 +458,7 @@ class RolloutCollector:
         import inspect
         self._values_out = "out" in inspect.signature(module.values).parameters
         self._ls: Optional[torch.Tensor] = None
+        self._head = bool(getattr(module, "head_mode", False))  # mu/sigma-head module (sample_actions)
         # obs_normalization "meanstd": RLlib's running filter, one per lane (env runner), synchronised
         # after every collect (marlsc/obs_filter.py)
         self.obs_filter = None
@@ -417,7 +531,9 @@ class RolloutCollector:
                                         self._noise_seed, self.noise_step + t)
         eps = ln.noise[t % chunk]
         a = None
-        if self._ls is not None and hasattr(m, "actor_sample"):
+        if self._head:  # state-dependent log_std: one row per row (head_sample)
+            a = m.sample_actions(obs, full, eps, self.actions[t, sl], self.logp[t, sl])
+        elif self._ls is not None and hasattr(m, "actor_sample"):
             # actor forward + sampling + log-density + the env's clip in one kernel launch
             clipped = torch.empty_like(self.actions[t, sl])
             if m.actor_sample(obs, full, (self._ls, m.rc.logstd_floor, eps, self.actions[t, sl], self.logp[t, sl],
