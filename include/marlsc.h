@@ -301,6 +301,10 @@ int msc_env_check(msc_env* env);
  *   A_t     = delta_t + gamma * lam * (1 - term_t) * (1 - trunc_t) * A_{t+1}
  * where V_{t+1} = next_values[t] if trunc_t (bootstrap from the terminal obs) else values[t+1];
  * values[T] (row T of `values`, [T+1][N]) bootstraps the last row. targets = A + V.
+ * All of it is float32, one rounding per operation and no fused multiply-add: gamma * lam is formed
+ * once in float32, delta_t = (r_t + gamma * V_{t+1}) - V_t, A_t = delta_t + (gamma * lam) * A_{t+1};
+ * a terminated step bootstraps 0 even when it is also truncated; next_values == NULL bootstraps 0 on
+ * truncated steps; terminated / truncated == NULL mean no flag set.
  * stats_out (device f64[3]) receives {sum A, sum A^2, count} (accumulated, caller zeroes it)
  * for the cross-rank advantage standardisation. */
 int msc_gae(const float* rewards, const float* values, const float* next_values,
@@ -338,7 +342,10 @@ int msc_gaussian_sample(const float* mean, const float* log_std, int32_t log_std
 /* Standard-normal rollout noise keyed by global env id (no reference counterpart: RLlib draws it from
  * torch's global generator per env runner). out [n_steps][n_rows][row_len] f32: element (s, row, j)
  * depends only on (seed, row0 + row, step0 + s, j) -- Philox4x32-10, Box-Muller -- so the noise of a
- * global env is the same whichever rank owns it and however the envs are sharded. */
+ * global env is the same whichever rank owns it and however the envs are sharded.
+ * Counter {j / 2, low word of row0 + row, its high word, (step0 + s) mod 2^32}, key {low word of
+ * seed, high word}; output words 0 and 1 give u1 = (w0 + 0.5) 2^-32 and u2 = w1 2^-32, elements
+ * 2 (j / 2) and 2 (j / 2) + 1 are sqrt(-2 log u1) times cos and sin of 2 pi u2. */
 int msc_normal_keyed(float* out, int32_t n_steps, int64_t n_rows, int32_t row_len, int64_t row0, uint64_t seed,
                      uint64_t step0, msc_stream_t stream);
 
