@@ -469,6 +469,40 @@ int msc_mlp2_relu_musigma(const float* x, int64_t n_rows, int32_t in_dim, int32_
                           const float* b1, const float* whp, const float* bh, const float* pre1, int32_t pre1_group,
                           const msc_musigma_epilogue* head, msc_stream_t stream);
 
+/* One time step of a GRU network for n_rows rows in one launch: replaces the module
+ * GRUArchitecture.build returns (architectures/gru.py:14-85: nn.GRU(batch_first) -> output_proj =
+ * [act,] Linear [, act]) as BaseRLModule._forward_gru steps it on a [B, obs_dim] input
+ * (rlmodules/base.py:99-141), the state laid out as get_initial_state gives it ([B, layers, hidden],
+ * base.py:351-388). Per layer, PyTorch's gate order and formula:
+ *   r = sigmoid(W_ir x + b_ir + W_hr h + b_hr)      z = sigmoid(W_iz x + b_iz + W_hz h + b_hz)
+ *   n = tanh(W_in x + b_in + r * (W_hn h + b_hn))   h' = (1 - z) * n + z * h
+ * layer 2 reads layer 1's h'; y = act_out(W_o act_pre(h'_last) + b_o) (MSC_ACT_* codes).
+ * x [n_rows][in_dim], h_in / h_out [n_rows][layers][hidden], y [n_rows][out_dim]: f32 device buffers,
+ * stream-ordered. h_out NULL: the new state is not stored (V(final_obs) bootstrap); h_out == h_in is an
+ * error (ping-pong two buffers). reset (optional, u8 [n_rows / reset_group]): rows whose group's flag
+ * is non-zero read h_in as zero (the env's truncation row of the previous step, reset_group = agents).
+ * The fused set (msc_gru_supported: 1 / 0): hidden in {64, 128, 256}, layers 1 or 2, in_dim <= 1024,
+ * out_dim <= 32 or a multiple of 32 up to 256. Packed weights (marlsc/gru.py:pack_gru), with
+ * rho(r, h) = (r & 3) + 8 (r >> 2) + 4 h, c = lane & 31, h = lane >> 5, NT = hidden / 32, gate rows in
+ * torch's order (tile T = gate NT + t covers rows 32 T .. 32 T + 31 of the [3 hidden][.] matrices):
+ *   wi[0] [3 NT][M4][64][4]: W_ih_l0[32 T + c][h KS + 4 m4 + i], KS = ceil(in_dim / 2), M4 = ceil(KS / 4),
+ *                            zero where 4 m4 + i >= KS or the column is past in_dim;
+ *   wi[1], wh[l] [3 NT][4 NT][64][4]: W[32 T + c][32 (s / 16) + rho(s % 16, h)], s = 4 s4 + i;
+ *   b[l] [4 hidden] = [b_ir + b_hr | b_iz + b_hz | b_in | b_hn];
+ *   wo [ceil(out_dim / 32)][4 NT][64][4]: W_o[32 q + c][32 (s / 16) + rho(s % 16, h)], zero for rows
+ *   past out_dim; bo [out_dim]. */
+typedef struct msc_gru_weights {
+  const float* wi[2];
+  const float* wh[2];
+  const float* b[2];
+  const float* wo;
+  const float* bo;
+} msc_gru_weights;
+int msc_gru_supported(int32_t in_dim, int32_t hidden, int32_t layers, int32_t out_dim);
+int msc_gru_step(const float* x, int64_t n_rows, int32_t in_dim, int32_t hidden, int32_t layers, int32_t out_dim,
+                 const float* h_in, const msc_gru_weights* w, int32_t act_pre, int32_t act_out, const uint8_t* reset,
+                 int32_t reset_group, float* y, float* h_out, msc_stream_t stream);
+
 /* Utility: numpy's Generator.poisson on the device (synchronous; the env's own sampler, exposed for
  * known-answer tests): n draws with the rates lam_host[i % n_lam] (random_poisson: multiplication
  * method below 10, PTRS at or above, numpy/random/src/distributions/distributions.c) from the PCG64

@@ -1572,6 +1572,43 @@ int msc_mlp2_relu_musigma(const float* x, int64_t n_rows, int32_t in_dim, int32_
   return 0;
 }
 
+// GRU networks (replaces GRUArchitecture's gru -> output_proj as BaseRLModule._forward_gru steps it,
+// architectures/gru.py:14-85, rlmodules/base.py:99-141)
+int msc_gru_supported(int32_t in_dim, int32_t hidden, int32_t layers, int32_t out_dim) {
+  return gru_supported(in_dim, hidden, layers, out_dim) ? 1 : 0;
+}
+
+int msc_gru_step(const float* x, int64_t n_rows, int32_t in_dim, int32_t hidden, int32_t layers, int32_t out_dim,
+                 const float* h_in, const msc_gru_weights* w, int32_t act_pre, int32_t act_out, const uint8_t* reset,
+                 int32_t reset_group, float* y, float* h_out, msc_stream_t stream) {
+  if (!x || !h_in || !w || !y) return set_err(-1, "null argument");
+  if (n_rows < 0) return set_err(-1, "n_rows %lld < 0", (long long)n_rows);
+  if (!gru_supported(in_dim, hidden, layers, out_dim))
+    return set_err(-1, "no fused GRU step for in_dim %d, hidden %d, layers %d, out_dim %d (hidden in {64, 128, 256}, "
+                   "1 or 2 layers, in_dim <= 1024, out_dim <= 32 or a multiple of 32 up to 256)", in_dim, hidden, layers,
+                   out_dim);
+  if (h_out == h_in) return set_err(-1, "h_out must not be h_in (ping-pong two buffers)");
+  auto act_ok = [](int a) { return a >= MSC_ACT_NONE && a <= MSC_ACT_SIGMOID; };
+  if (!act_ok(act_pre) || !act_ok(act_out)) return set_err(-1, "activation codes %d, %d: must be MSC_ACT_* (0..5)", act_pre, act_out);
+  if (reset && (reset_group < 1 || n_rows % reset_group != 0))
+    return set_err(-1, "reset_group %d must be >= 1 and divide n_rows %lld", reset_group, (long long)n_rows);
+  GruWeights gw{};
+  uintptr_t al = (uintptr_t)h_in | (uintptr_t)h_out | (uintptr_t)w->wo;
+  for (int l = 0; l < layers; l++) {
+    if (!w->wi[l] || !w->wh[l] || !w->b[l]) return set_err(-1, "null weight buffer of layer %d", l);
+    gw.wi[l] = w->wi[l], gw.wh[l] = w->wh[l], gw.b[l] = w->b[l];
+    al |= (uintptr_t)w->wi[l] | (uintptr_t)w->wh[l] | (uintptr_t)w->b[l];
+  }
+  if (!w->wo || !w->bo) return set_err(-1, "null output-projection buffer");
+  if (out_dim % 4 == 0) al |= (uintptr_t)y;  // (stored as float4)
+  // the kernel reads the state, the biases and the packed weights as float4, and stores the state so
+  if (al & 15) return set_err(-1, "h_in, h_out, y (out_dim a multiple of 4), the biases and the packed weights must be 16-byte aligned");
+  gw.wo = w->wo, gw.bo = w->bo;
+  HIP_TRY(launch_gru_step(x, n_rows, in_dim, hidden, layers, out_dim, h_in, gw, act_pre, act_out, reset,
+                          reset ? reset_group : 1, y, h_out, (hipStream_t)stream));
+  return 0;
+}
+
 int msc_adv_normalize_grouped(float* adv, int64_t n, int32_t n_groups, const double* stats, msc_stream_t stream) {
   if (!adv || !stats || n < 0) return set_err(-1, "bad argument");
   if (n_groups < 1 || n_groups > 64 || n % n_groups != 0)

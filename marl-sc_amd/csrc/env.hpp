@@ -280,6 +280,18 @@ hipError_t launch_mlp3_musigma(const float* x, int64_t n, int L, int H1, int H2,
 hipError_t launch_mlp2_musigma(const float* x, int64_t n, int L, int H1, int K, const float* w1p, const float* b1,
                                const float* whp, const float* bh, const float* pre1, int grp, hipStream_t st,
                                const MlpMuSigma& ep);
+// the fused GRU step's packed weight set (msc_gru_weights; gru.hip)
+struct GruWeights {
+  const float* wi[2];  // per layer: W_ih fragments
+  const float* wh[2];  // per layer: W_hh fragments
+  const float* b[2];   // per layer: [b_ir + b_hr | b_iz + b_hz | b_in | b_hn]
+  const float* wo;     // output projection fragments
+  const float* bo;     // [out_dim]
+};
+bool gru_supported(int L, int H, int layers, int KO);
+hipError_t launch_gru_step(const float* x, int64_t n, int L, int H, int layers, int KO, const float* h_in,
+                           const GruWeights& w, int act_pre, int act_out, const uint8_t* reset, int grp, float* y,
+                           float* h_out, hipStream_t st);
 hipError_t launch_normal_keyed(float* out, int32_t n_steps, int64_t n_rows, int32_t row_len, int64_t row0,
                                uint64_t seed, uint64_t step0, hipStream_t st);
 hipError_t launch_meanstd_filter(const float* x, float* out, int64_t E, int32_t C, const uint8_t* mask, int32_t update,

@@ -92,6 +92,12 @@ class MscMuSigmaEpilogue(C.Structure):
                 ("clipped", C.c_void_p), ("dist_out", C.c_void_p)]
 
 
+class MscGruWeights(C.Structure):
+    """msc_gru_weights (include/marlsc.h): the fused GRU step's packed weight set."""
+    _fields_ = [("wi", C.c_void_p * 2), ("wh", C.c_void_p * 2), ("b", C.c_void_p * 2), ("wo", C.c_void_p),
+                ("bo", C.c_void_p)]
+
+
 def lib() -> C.CDLL:
     """Load libmarlsc.so (built by __graft_entry__.build()). Raises if it is missing."""
     global _LIB
@@ -153,6 +159,9 @@ def lib() -> C.CDLL:
                                         vp, vp, C.c_int32, P(MscMuSigmaEpilogue), vp]
     L.msc_mlp2_relu_musigma.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, C.c_int32,
                                         P(MscMuSigmaEpilogue), vp]
+    L.msc_gru_supported.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+    L.msc_gru_step.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, P(MscGruWeights), C.c_int32,
+                               C.c_int32, vp, C.c_int32, vp, vp, vp]
     L.msc_meanstd_scratch_doubles.argtypes = [C.c_int64, C.c_int32]
     L.msc_meanstd_scratch_doubles.restype = C.c_int64
     L.msc_meanstd_filter.argtypes = [vp, vp, C.c_int64, C.c_int32, vp, C.c_int32, vp, vp, C.c_double, C.c_double, vp]
@@ -178,5 +187,6 @@ EXPORTED_SYMBOLS = [
     "msc_env_set_episode_counters", "msc_gae", "msc_adv_normalize", "msc_gae_grouped", "msc_adv_normalize_grouped", "msc_gaussian_sample", "msc_mlp3_w3_layout", "msc_mlp3_relu_forward", "msc_mlp2_relu_forward",
     "msc_mlp3_relu_forward_sampled", "msc_mlp2_relu_forward_sampled",
     "msc_mlp_musigma_layout", "msc_mlp3_relu_musigma", "msc_mlp2_relu_musigma",
+    "msc_gru_supported", "msc_gru_step",
     "msc_normal_keyed", "msc_poisson_draws", "msc_meanstd_scratch_doubles", "msc_meanstd_filter", "msc_seedseq_u32", "msc_last_error", "msc_abi_version",
 ]

@@ -239,7 +239,8 @@ def run_evaluate(args) -> Dict[str, Any]:
         import numpy as np
         env_meta["obs_stats"] = (np.asarray(state["obs_stats"][0], np.float32), np.asarray(state["obs_stats"][1], np.float32))
     root_seed = meta["root_seed"] if args.root_seed is None else args.root_seed
-    trainer = PPOTrainer(env_cfg, cfg, root_seed=root_seed, n_envs=1, rollout_len=1,
+    # the smallest rollout the trainer accepts (one chunk of max_seq_len steps with GRU networks); unused
+    trainer = PPOTrainer(env_cfg, cfg, root_seed=root_seed, n_envs=1, rollout_len=cfg.rollout_config().max_seq_len or 1,
                          device=0 if args.device is None else args.device, env_meta=env_meta, eval_seed=args.eval_seed)
     trainer.load_checkpoint(ckpt, runtime=False)  # weights only: evaluation builds its own envs
     n = args.eval_episodes or DEFAULT_EVAL_EPISODES

@@ -145,6 +145,9 @@ class _Pack:
     def __init__(self):
         self.key, self.tensors, self.stream, self.event = None, None, None, None
 
+    def __deepcopy__(self, memo):  # a copied module packs its own weights (streams / events do not copy)
+        return _Pack()
+
 
 def _cached_pack(l1: nn.Module, slot, weights, cur, build):
     """The head actors' pack cached on the first Linear under `slot`, by mlp3_forward's rules: rebuilt

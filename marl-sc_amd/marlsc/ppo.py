@@ -51,8 +51,9 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from . import dist as mdist
-from .rollout import (LOG_STD_MIN, MLP, RolloutCollector, RolloutConfig, build_actor, check_head_config,
-                      fused_actor_sample, gaussian_sample, head_sample, mlp_forward, split_global_mlp)
+from .rollout import (LOG_STD_MIN, PolicyNets, RecurrentAPI, RolloutCollector, RolloutConfig, check_gru_config,
+                      check_head_config, fused_actor_sample, gaussian_sample, head_sample, mlp_forward, network_types,
+                      split_global_mlp)
 
 LOG2PI = math.log(2 * math.pi)
 ENTROPY_CONST = 0.5 * math.log(2 * math.pi * math.e)
@@ -124,14 +125,14 @@ class PPOConfig:
 
     def rollout_config(self) -> RolloutConfig:
         nets = self.networks or {}
-        if nets.get("shared_layers"):
-            raise ValueError("shared_layers (GRU) networks are outside this build's training path")
         head = check_head_config(nets)
+        check_gru_config(nets, self.actor_obs_type, self.critic_obs_type, self.batch_size, self.num_minibatches)
         return RolloutConfig(gamma=float(self.gamma), lam=float(self.lam) if self.use_gae else 1.0,
                              actor_obs_type=self.actor_obs_type, critic_obs_type=self.critic_obs_type,
                              logstd_init=float(self.logstd_init), logstd_floor=float(self.logstd_floor),
                              actor=(nets.get("actor") or {}).get("config"),
-                             critic=(nets.get("critic") or {}).get("config"), use_mu_sigma_head=head)
+                             critic=(nets.get("critic") or {}).get("config"), use_mu_sigma_head=head,
+                             **network_types(nets))
 
     def lr_at(self, timestep: int) -> float:
         """RLlib learning-rate schedule: piecewise linear over [[t, lr], ...], constant outside."""
@@ -150,30 +151,25 @@ class PPOConfig:
 # ----------------------------------------------------------------------------------------------
 # modules: one shared policy or one per agent (the reference's policy mapping, mappo.py:102-113)
 # ----------------------------------------------------------------------------------------------
-class AgentModule(nn.Module):
-    """ActorCriticRLModule for MLP networks (rlmodules/base.py:480-715). use_mu_sigma_head: the actor
-    is the backbone under `mu_sigma_head` and there is no `log_std` parameter (base.py:213-252)."""
+class AgentModule(PolicyNets, nn.Module):
+    """ActorCriticRLModule (rlmodules/base.py:150-262, 480-715): MLP or GRU actor / critic, optionally
+    on a shared GRU trunk `shared_layers` (rollout.PolicyNets). use_mu_sigma_head: the actor is the
+    backbone under `mu_sigma_head` and there is no `log_std` parameter (base.py:213-252)."""
 
     def __init__(self, local_obs_dim: int, global_obs_dim: int, action_dim: int, rc: RolloutConfig):
         super().__init__()
-        full = local_obs_dim + global_obs_dim
-        self.actor, head = build_actor(full if rc.actor_obs_type == "global" else local_obs_dim, action_dim, rc,
-                                       {"hidden_sizes": [256, 256]})
-        self.head_mode = head is not None
-        if self.head_mode:
-            self.mu_sigma_head = head
-        self.critic = MLP(full if rc.critic_obs_type == "global" else local_obs_dim, 1,
-                          rc.critic or {"hidden_sizes": [256, 256]})
-        if not self.head_mode:
-            self.log_std = nn.Parameter(torch.full((action_dim,), float(rc.logstd_init)))
+        self._build_nets(local_obs_dim, global_obs_dim, action_dim, rc, {"hidden_sizes": [256, 256]},
+                         {"hidden_sizes": [256, 256]})
 
     def dist(self, x: torch.Tensor):
         """Head mode: (mu, log_std) of the actor input x through the torch layers."""
         return self.mu_sigma_head(self.actor(x))
 
 
-class MultiAgentActorCritic(nn.Module):
-    """dist_inputs / values over [..., W, obs] for the shared policy or W per-agent policies."""
+class MultiAgentActorCritic(RecurrentAPI, nn.Module):
+    """dist_inputs / values over [..., W, obs] for the shared policy or W per-agent policies. With GRU
+    networks the stateless entry points (dist_inputs / actor_mean / values) do not apply: the state
+    is threaded through RecurrentAPI's initial_state / step / sequence."""
 
     def __init__(self, n_agents: int, local_obs_dim: int, global_obs_dim: int, action_dim: int, rc: RolloutConfig,
                  shared: bool):
@@ -186,6 +182,29 @@ class MultiAgentActorCritic(nn.Module):
     def _x(self, local_obs, full_obs, kind):
         return full_obs if kind == "global" else local_obs
 
+    def _policy_list(self):
+        return list(self.policies)
+
+    def actor_sample_x(self, x: torch.Tensor, sample) -> bool:
+        """actor_sample on the actor's own input x (the trunk's features with shared layers)."""
+        return self.shared and fused_actor_sample(self.policies[0].actor, x, sample)
+
+    def sample_actions_x(self, x, eps, actions, logp) -> torch.Tensor:
+        if self.shared:
+            return head_sample(self.policies[0].actor, self.policies[0].mu_sigma_head, x, eps, actions, logp)
+        mu, ls = self.sample_dist_x(x)
+        return gaussian_sample(mu.contiguous(), ls.contiguous(), LOG_STD_MIN, eps, actions, logp)
+
+    def actor_mean_x(self, x: torch.Tensor) -> torch.Tensor:
+        return self._per_agent(lambda p, v: p.actor(v), x)
+
+    def sample_dist_x(self, x: torch.Tensor):
+        """Head mode: (mu, log_std) of the actor input x through the torch layers."""
+        if self.shared:
+            return self.policies[0].dist(x)
+        d = [p.dist(x[..., w, :]) for w, p in enumerate(self.policies)]
+        return torch.stack([m for m, _ in d], dim=-2), torch.stack([s for _, s in d], dim=-2)
+
     def _per_agent(self, fn, x):
         if self.shared:
             return fn(self.policies[0], x)
@@ -194,7 +213,8 @@ class MultiAgentActorCritic(nn.Module):
     def actor_mean(self, local_obs, full_obs=None):
         if self.head_mode:
             return self.dist_inputs(local_obs, full_obs)[0]
-        return self._per_agent(lambda p, v: p.actor(v), self._x(local_obs, full_obs, self.rc.actor_obs_type))
+        self._stateless()
+        return self.actor_mean_x(self._x(local_obs, full_obs, self.rc.actor_obs_type))
 
     def log_std_table(self) -> Optional[torch.Tensor]:
         """[P, K] unclamped log_std rows (P = 1 shared, W per agent) for msc_gaussian_sample, which
@@ -205,26 +225,17 @@ class MultiAgentActorCritic(nn.Module):
 
     def actor_sample(self, local_obs, full_obs, sample) -> bool:
         """Shared policy: the actor with the rollout's action sampling fused into its kernel."""
-        if not self.shared:
-            return False
-        return fused_actor_sample(self.policies[0].actor, self._x(local_obs, full_obs, self.rc.actor_obs_type), sample)
+        return self.actor_sample_x(self._x(local_obs, full_obs, self.rc.actor_obs_type), sample)
 
     def sample_actions(self, local_obs, full_obs, eps, actions, logp) -> torch.Tensor:
         """Head mode: one rollout step's actor forward and sampling. The shared policy takes the
         fused paths of rollout.head_sample; per-agent policies run the torch layers."""
-        x = self._x(local_obs, full_obs, self.rc.actor_obs_type)
-        if self.shared:
-            return head_sample(self.policies[0].actor, self.policies[0].mu_sigma_head, x, eps, actions, logp)
-        mu, ls = self.dist_inputs(local_obs, full_obs)
-        return gaussian_sample(mu.contiguous(), ls.contiguous(), LOG_STD_MIN, eps, actions, logp)
+        return self.sample_actions_x(self._x(local_obs, full_obs, self.rc.actor_obs_type), eps, actions, logp)
 
     def dist_inputs(self, local_obs, full_obs=None):
+        self._stateless()
         if self.head_mode:  # (mu, log_std) per row through the torch layers
-            x = self._x(local_obs, full_obs, self.rc.actor_obs_type)
-            if self.shared:
-                return self.policies[0].dist(x)
-            d = [p.dist(x[..., w, :]) for w, p in enumerate(self.policies)]
-            return torch.stack([m for m, _ in d], dim=-2), torch.stack([s for _, s in d], dim=-2)
+            return self.sample_dist_x(self._x(local_obs, full_obs, self.rc.actor_obs_type))
         floor = self.rc.logstd_floor
         mean = self.actor_mean(local_obs, full_obs)
         if self.shared:
@@ -235,6 +246,7 @@ class MultiAgentActorCritic(nn.Module):
         return mean, log_std
 
     def values(self, local_obs, full_obs=None, out=None):
+        self._stateless()
         if self.rc.critic_obs_type == "global" and full_obs is None:  # split first layer (rollout.py)
             if self.shared:
                 return split_global_mlp(self.policies[0].critic, local_obs, out=out).squeeze(-1)
@@ -371,17 +383,79 @@ class PPOLearner:
         values = policy.critic(full if rc.critic_obs_type == "global" else local).squeeze(-1)
         return mean, log_std, values
 
+    # -- GRU networks: a training sample is a sequence (chunk c, env e, agent w) of S = max_seq_len
+    # consecutive rollout steps, id (c E + e) W + w; its rows are the flat ids ((c S + s) E + e) W + w --
+    def _seq_ids(self, C: int, E: int, W: int, device) -> List[torch.Tensor]:
+        if self.module.shared:
+            return [torch.arange(C * E * W, device=device)]
+        return [torch.arange(C * E, device=device) * W + w for w in range(W)]
+
+    def _seq_forward(self, policy: "AgentModule", obs: torch.Tensor, seq: Dict[str, Any], ids: torch.Tensor):
+        """(mean, log_std, values, flat row ids), each over the B S rows of sequences `ids`: the chunk's
+        forward from the detached state_in, the state multiplied by 1 - truncated[t - 1] inside the
+        chunk, with autograd through at most S steps."""
+        rc = self.module.rc
+        T, E, S = seq["T"], seq["E"], seq["S"]
+        W, L = obs.shape[1], obs.shape[2]
+        w = ids % W
+        e = torch.div(ids, W, rounding_mode="floor") % E
+        c = torch.div(ids, W * E, rounding_mode="floor")
+        t = c[:, None] * S + torch.arange(S, device=ids.device)[None, :]          # [B, S] rollout steps
+        env_rows = t * E + e[:, None]                                               # rows of obs [T E, W, L]
+        rows = env_rows * W + w[:, None]                                            # flat (T E W) ids
+        local = obs.reshape(T * E * W, L)[rows]                                     # [B, S, L]
+        full = None
+        if rc.actor_obs_type == "global" or rc.critic_obs_type == "global":
+            full = torch.cat([local, obs.reshape(T * E, W * L)[env_rows]], dim=-1)
+        trunc = seq["truncated"].reshape(T * E * W)
+        keep = torch.ones(rows.shape, device=ids.device)
+        if S > 1:
+            keep[:, 1:] = (trunc[rows[:, :-1]] == 0).to(keep.dtype)
+        if bool((keep == 1).all()):
+            keep = None  # reset-free chunks: one nn.GRU call over the whole sequence
+        h0 = {k: h.reshape(-1, *h.shape[3:])[ids].detach() for k, h in seq["state_in"].items()}
+        mean, log_std, values = policy.sequence_rows(full if rc.actor_obs_type == "global" else local,
+                                                     full if rc.critic_obs_type == "global" else local, h0, keep,
+                                                     rc.logstd_floor)
+        K = mean.shape[-1]
+        return mean.reshape(-1, K), log_std.reshape(-1, K), values.reshape(-1), rows.reshape(-1)
+
     def update(self, batch: Dict[str, torch.Tensor], full_fn=None, timestep: int = 0) -> Dict[str, float]:
         """batch tensors are [S, W, ...] (S env samples of W agents). full_fn is unused (the learner
-        gathers each row's local || global observation itself) and kept for call compatibility."""
+        gathers each row's local || global observation itself) and kept for call compatibility.
+        With GRU networks the rows are T x E in rollout order and batch["seq"] = {"T", "E", "S",
+        "state_in": {slot: [T / S, E, W, layers, hidden]}, "truncated": [T, E, W]}."""
         cfg, m = self.cfg, self.module
         for g in self.opt.param_groups:
             g["lr"] = cfg.lr_at(timestep)
         obs = batch["obs"]
         S, W = obs.shape[0], obs.shape[1]
-        flat = {k: v.reshape(S * W, *v.shape[2:]) for k, v in batch.items() if k != "obs"}
+        seq = batch.get("seq") if getattr(m, "recurrent", False) else None
+        if getattr(m, "recurrent", False):
+            if seq is None:
+                raise ValueError("GRU networks: the batch needs 'seq' (T, E, S, state_in, truncated)")
+            if seq["T"] % seq["S"] != 0:
+                raise ValueError(f"rollout length T = {seq['T']} must be a multiple of max_seq_len = {seq['S']}")
+            if seq["T"] * seq["E"] != S:
+                raise ValueError(f"batch has {S} env rows, seq says T x E = {seq['T']} x {seq['E']}")
+        flat = {k: v.reshape(S * W, *v.shape[2:]) for k, v in batch.items() if k not in ("obs", "seq")}
         mb = minibatch_rows(cfg, self.world)
-        streams = [_CyclicRows(r, min(mb, r.numel()), self.gen) for r in self._module_rows(S, W, obs.device)]
+        if seq is not None:
+            n_seq = max(1, mb // seq["S"])
+            streams = [_CyclicRows(r, min(n_seq, r.numel()), self.gen)
+                       for r in self._seq_ids(seq["T"] // seq["S"], seq["E"], W, obs.device)]
+            if cfg.use_kl_loss:  # the old distribution from the same sequence forward, before any step
+                K = flat["actions"].shape[-1]
+                flat["mean_old"] = torch.empty((S * W, K), device=obs.device)
+                flat["log_std_old"] = torch.empty((S * W, K), device=obs.device)
+                with torch.no_grad():
+                    for pol, st in zip(m.policies, streams):
+                        for ids in st.rows.split(4096):
+                            mo, lo, _, rows = self._seq_forward(pol, obs, seq, ids)
+                            flat["mean_old"][rows], flat["log_std_old"][rows] = mo, lo
+        else:
+            streams = [_CyclicRows(r, min(mb, r.numel()), self.gen) for r in self._module_rows(S, W, obs.device)]
+        self.last_minibatch_sizes = [st.mb for st in streams]
         acc: Dict[str, float] = {}
         kl_sum = [0.0] * len(streams)
         n = 0
@@ -390,8 +464,12 @@ class PPOLearner:
             mstats: Dict[str, torch.Tensor] = {}
             for j, (pol, st) in enumerate(zip(m.policies, streams)):
                 idx = st.next()
-                b = {k: v[idx] for k, v in flat.items()}
-                mean, log_std, values = self._forward(pol, obs, idx)
+                if seq is not None:
+                    mean, log_std, values, idx = self._seq_forward(pol, obs, seq, idx)
+                    b = {k: v[idx] for k, v in flat.items()}
+                else:
+                    b = {k: v[idx] for k, v in flat.items()}
+                    mean, log_std, values = self._forward(pol, obs, idx)
                 loss, sts = ppo_loss(cfg, mean, log_std, values, b, self.kl_coeffs[j])
                 total = loss if total is None else total + loss
                 if "mean_kl" in sts:
@@ -543,13 +621,18 @@ class PPOTrainer:
         self.E = E
         # rollout length: RLlib's train batch counts env steps over every runner of every rank
         self.T = int(rollout_len or max(1, math.ceil(cfg.batch_size / (E * self.world))))
+        rc = cfg.rollout_config()
+        if rc.max_seq_len:  # GRU networks train on chunks of max_seq_len steps: a derived T is rounded up
+            # to whole chunks (RLlib pads the last chunk of each episode fragment instead)
+            if rollout_len and self.T % rc.max_seq_len:
+                raise ValueError(f"rollout_len = {self.T} must be a multiple of max_seq_len = {rc.max_seq_len}")
+            self.T = -(-self.T // rc.max_seq_len) * rc.max_seq_len
         self.device = torch.device("cuda", device)
         # weak partition: rank g steps global env ids [g E, (g + 1) E); ranks sharing a device split
         # the episode-ahead memory budget
         self.env = VecInventoryEnv(None, E, spec=self.spec, device=device, base_seed=self.train_seed,
                                    env_index_offset=mdist.shard(E, "weak", self.rank, self.world)[1],
                                    ea_mem_fraction=mdist.ea_mem_fraction())
-        rc = cfg.rollout_config()
         torch.manual_seed(self.train_seed)
         W, L = self.env.W, self.env.local_obs_dim
         self.module = MultiAgentActorCritic(W, L, L * W, self.env.K, rc, cfg.parameter_sharing).to(self.device)
@@ -573,8 +656,8 @@ class PPOTrainer:
         self._n_episodes = 0
 
     def _full_fn(self):
-        if self.cfg.actor_obs_type != "global":  # the critic evaluates its split first layer
-            return None
+        if self.cfg.actor_obs_type != "global" and not (self.module.recurrent and self.cfg.critic_obs_type == "global"):
+            return None  # the critic evaluates its split first layer
         W, L = self.env.W, self.env.local_obs_dim
 
         def full(obs):  # obs [S, W, L] of S whole envs -> local || global per agent
@@ -599,7 +682,10 @@ class PPOTrainer:
         batch = {"obs": out["obs"].reshape(T * E, W, -1), "actions": out["actions"].reshape(T * E, W, -1),
                  "logp": out["logp"].reshape(T * E, W), "advantages": out["advantages"].reshape(T * E, W),
                  "value_targets": out["value_targets"].reshape(T * E, W)}
-        if cfg.use_kl_loss:
+        if self.module.recurrent:  # sequences of max_seq_len steps (the learner computes the KL's old dist)
+            batch["seq"] = {"T": T, "E": E, "S": int(self.module.max_seq_len), "state_in": out["state_in"],
+                            "truncated": out["truncated"]}
+        elif cfg.use_kl_loss:
             with torch.no_grad():
                 mo, lo = self.module.dist_inputs(batch["obs"], self._full_fn()(batch["obs"]) if self._full_fn() else None)
             batch["mean_old"], batch["log_std_old"] = mo, lo
@@ -650,11 +736,17 @@ class PPOTrainer:
         full_fn = self._full_fn()
         filt = self.collector.obs_filter  # "meanstd": the trained filter with update=False
         ret = torch.zeros(n, dtype=torch.float64, device=self.device)
+        state = self.module.initial_state(n, device=self.device) if self.module.recurrent else None
         for _ in range(spec.episode_length):
             if filt is not None:
                 obs = filt.normalize(obs)
             full = env.obs_flat(obs=obs) if full_fn is not None else None
-            mean, _ = self.module.dist_inputs(obs, full)
+            if state is not None:  # the state carried from zero through the episode
+                a_in, mean, _, state = self.module.step(obs, full, state, critic=False)
+                if mean is None:
+                    mean = (self.module.sample_dist_x(a_in)[0] if self.module.head_mode else self.module.actor_mean_x(a_in))
+            else:
+                mean, _ = self.module.dist_inputs(obs, full)
             obs, rew, trunc, _ = env.step(mean.clamp(-1.0, 1.0).contiguous())
             ret += rew.double().sum(-1)
         env.close()
@@ -689,6 +781,7 @@ class PPOTrainer:
                     "noise_step": int(self.collector.noise_step), "learner_gen": self.learner.gen.get_state(),
                     "ep_ret": self._ep_ret.detach().cpu(), "completed": list(self._completed),
                     "n_episodes": self._n_episodes,
+                    "gru_state": {k: h.detach().cpu() for k, h in self.collector.state.items()},
                     "obs_filtered": [bool(ln.obs_filtered) for ln in self.collector._lanes]},
                    p / f"runtime_rank{self.rank}.pt")
         return p
@@ -747,5 +840,9 @@ class PPOTrainer:
         self._ep_ret.copy_(rt["ep_ret"].to(self.device))
         self._completed = deque((float(x) for x in rt["completed"]), maxlen=self._completed.maxlen)
         self._n_episodes = int(rt["n_episodes"])
+        if self.collector.state:
+            if "gru_state" not in rt:
+                raise ValueError(f"{p}: GRU networks but the runtime checkpoint holds no recurrent state")
+            self.collector.load_state(rt["gru_state"])
         for ln, f in zip(self.collector._lanes, rt.get("obs_filtered", [])):
             ln.obs_filtered = bool(f)

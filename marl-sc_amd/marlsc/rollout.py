@@ -11,6 +11,9 @@ unpinned against the reference and checked against the numpy GAE in oracle/gae_r
   clamped at `logstd_floor` (`_append_log_std`), critic on local (IPPO) or full flat obs (MAPPO);
   with `use_mu_sigma_head` the actor is a backbone under `MuSigmaHead` (base.py:213-252, :434-435;
   architectures/mu_sigma_head.py) and log_std depends on the observation (`head_sample`);
+* `GRUNet` / `PolicyNets`: the `gru` architecture (architectures/gru.py:14-85) as actor, critic or shared
+  trunk, its states threaded through step / sequence forwards (base.py:99-141, 351-388, 480-715); one
+  fused launch per network and rollout step (marlsc/gru.py, csrc/gru.hip);
 * GAE(gamma, lambda) with truncation bootstrap V(final_obs) and RLlib's per-batch standardisation
   `(A - mean) / max(1e-4, std)`, statistics all-reduced across ranks (marlsc/dist.py).
 
@@ -55,6 +58,105 @@ class MLP(nn.Sequential):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         return mlp_forward(self, x)
+
+
+class GRUNet(nn.ModuleDict):
+    """The reference's `gru` architecture (architectures/gru.py:14-85): {"gru": nn.GRU(batch_first),
+    "output_proj": Linear, or Sequential([act,] Linear [, out_act]) when `activation` /
+    `output_activation` are set}, stepped as BaseRLModule._forward_gru does (rlmodules/base.py:99-141)
+    with the state laid out [rows, num_layers, hidden]. Unidirectional, no dropout."""
+
+    def __init__(self, in_dim: int, out_dim: int, config: Dict[str, Any]):
+        cfg = config or {}
+        if cfg.get("bidirectional", False):
+            raise ValueError("gru: bidirectional GRUs are not supported")
+        if float(cfg.get("dropout", 0.0) or 0.0) > 0.0:
+            raise ValueError("gru: dropout > 0 is not supported")
+        hidden, layers = int(cfg.get("hidden_size", 128)), int(cfg.get("num_layers", 2))
+        gru = nn.GRU(input_size=in_dim, hidden_size=hidden, num_layers=layers, batch_first=True)
+        proj = []
+        if cfg.get("activation"):
+            proj.append(_act(cfg["activation"]))
+        proj.append(nn.Linear(hidden, out_dim))
+        if cfg.get("output_activation"):
+            proj.append(_act(cfg["output_activation"]))
+        super().__init__({"gru": gru, "output_proj": nn.Sequential(*proj) if len(proj) > 1 else proj[0]})
+        self.in_dim, self.out_dim, self.hidden, self.layers = int(in_dim), int(out_dim), hidden, layers
+        self.max_seq_len = int(cfg["max_seq_len"]) if cfg.get("max_seq_len") is not None else None
+
+    def zero_state(self, *lead: int, device=None) -> torch.Tensor:
+        dev = device if device is not None else next(self.parameters()).device
+        return torch.zeros(*lead, self.layers, self.hidden, device=dev)
+
+    def step(self, x: torch.Tensor, h: torch.Tensor, reset: Optional[torch.Tensor] = None, group: int = 1, *,
+             store_state: bool = True, h_out: Optional[torch.Tensor] = None):
+        """One time step: x [..., in], h [..., layers, hidden] -> (y [..., out], h' or None); rows whose
+        group's reset flag is non-zero start from zero. One fused launch at rollout (marlsc/gru.py)."""
+        from .gru import gru_step_forward
+        return gru_step_forward(self, x, h, reset, group, store_state=store_state, h_out=h_out)
+
+    def sequence(self, x: torch.Tensor, h0: torch.Tensor, keep: Optional[torch.Tensor] = None):
+        """x [B, S, in] from the state h0 [B, layers, hidden] through the torch layers (autograd as
+        enabled): (y [B, S, out], final state). keep [B, S] multiplies the state entering step s
+        (0 = the row starts a new episode there); without resets the whole chunk is one nn.GRU call."""
+        g = self["gru"]
+        h = h0.transpose(0, 1).contiguous()
+        if keep is None:
+            o, h = g(x, h)
+        else:
+            outs = []
+            for s in range(x.shape[1]):
+                h = h * keep[:, s].to(h.dtype)[None, :, None]
+                o, h = g(x[:, s:s + 1], h)
+                outs.append(o)
+            o = torch.cat(outs, dim=1)
+        return self["output_proj"](o), h.transpose(0, 1)
+
+
+def check_gru_config(nets: Dict[str, Any], actor_obs_type: str, critic_obs_type: str,
+                     batch_size: Optional[int] = None, num_minibatches: Optional[int] = None) -> Optional[int]:
+    """The schema's recurrent-network rules (config/schema.py:923-957, 969-978, 1143-1151, 1284-1313) on
+    a `networks` dict; returns the common max_seq_len, or None when no network is a GRU."""
+    nets = nets or {}
+    sl = nets.get("shared_layers")
+    seq = []
+    for name in ("shared_layers", "actor", "critic"):
+        d = nets.get(name) or {}
+        typ = d.get("type", "mlp") if d else "mlp"
+        if name == "shared_layers":
+            if not sl:
+                continue
+            if typ != "gru":
+                raise ValueError(f"shared_layers: type '{typ}' is not supported (only gru shared layers)")
+        elif typ not in ("mlp", "gru"):
+            raise ValueError(f"{name}: network type '{typ}' is not supported (mlp or gru)")
+        if typ != "gru":
+            continue
+        c = d.get("config") or {}
+        if c.get("max_seq_len") is None:
+            raise ValueError(f"{name}: max_seq_len is required for gru networks")
+        if int(c["max_seq_len"]) < 1:
+            raise ValueError(f"{name}: max_seq_len must be >= 1")
+        if c.get("bidirectional", False):
+            raise ValueError(f"{name}: bidirectional GRUs are not supported")
+        if float(c.get("dropout", 0.0) or 0.0) > 0.0:
+            raise ValueError(f"{name}: dropout > 0 is not supported")
+        seq.append(int(c["max_seq_len"]))
+    if sl:
+        if (sl.get("config") or {}).get("output_dim") is None:
+            raise ValueError("shared_layers: config.output_dim is required")
+        if actor_obs_type != critic_obs_type:
+            raise ValueError("shared_layers requires actor_obs_type == critic_obs_type "
+                             f"(got '{actor_obs_type}' and '{critic_obs_type}')")
+    if not seq:
+        return None
+    if len(set(seq)) > 1:
+        raise ValueError(f"all gru networks must share one max_seq_len (got {sorted(set(seq))})")
+    if batch_size is not None and num_minibatches is not None and \
+            int(batch_size) // max(1, int(num_minibatches)) < seq[0]:
+        raise ValueError(f"minibatch size batch_size // num_minibatches = {int(batch_size) // max(1, int(num_minibatches))} "
+                         f"must be >= max_seq_len = {seq[0]}")
+    return seq[0]
 
 
 LOG_STD_MIN, LOG_STD_MAX = -4.6, 4.6  # MuSigmaHead.LOG_STD_MIN / LOG_STD_MAX (mu_sigma_head.py:22-23)
@@ -122,6 +224,133 @@ def build_actor(in_dim: int, action_dim: int, rc: "RolloutConfig", default: Dict
     return MLP(in_dim, dim, cfg), MuSigmaHead(dim, action_dim, act_mu, act_sigma)
 
 
+def network_types(nets: Dict[str, Any]) -> Dict[str, Any]:
+    """RolloutConfig's actor_type / critic_type / shared_layers fields of a `networks` dict."""
+    sl = (nets or {}).get("shared_layers")
+    return {"actor_type": ((nets or {}).get("actor") or {}).get("type", "mlp") or "mlp",
+            "critic_type": ((nets or {}).get("critic") or {}).get("type", "mlp") or "mlp",
+            "shared_layers": dict(sl.get("config") or {}) if sl else None}
+
+
+STATE_SLOTS = ("shared_h", "actor_h", "critic_h")  # the reference's state keys (rlmodules/base.py:351-388)
+
+
+class PolicyNets:
+    """One policy's networks as ActorCriticRLModule.setup builds them (rlmodules/base.py:150-262): an
+    optional GRU trunk `shared_layers` on the raw actor observation whose output_dim features feed
+    both actor and critic (base.py:196-210), an actor (MLP, MLP backbone under `mu_sigma_head`, or
+    GRU) and a critic (MLP or GRU), then the free `log_std` unless the head is used. Mixed into the
+    nn.Modules that hold them. MLP-only configs build parameter for parameter as before."""
+
+    def _build_nets(self, local_obs_dim: int, global_obs_dim: int, action_dim: int, rc: "RolloutConfig",
+                    default_actor: Dict[str, Any], default_critic: Dict[str, Any]) -> None:
+        full = local_obs_dim + global_obs_dim
+        a_in = full if rc.actor_obs_type == "global" else local_obs_dim
+        c_in = full if rc.critic_obs_type == "global" else local_obs_dim
+        if rc.shared_layers is not None:
+            self.shared_layers = GRUNet(a_in, int(rc.shared_layers["output_dim"]), rc.shared_layers)
+            a_in = c_in = int(rc.shared_layers["output_dim"])
+        if rc.actor_type == "gru":
+            self.actor, head = GRUNet(a_in, action_dim, rc.actor or {}), None
+        else:
+            self.actor, head = build_actor(a_in, action_dim, rc, default_actor)
+        self.head_mode = head is not None
+        if self.head_mode:
+            self.mu_sigma_head = head
+        if rc.critic_type == "gru":
+            self.critic = GRUNet(c_in, 1, rc.critic or {})
+        else:
+            self.critic = MLP(c_in, 1, rc.critic or default_critic)
+        if not self.head_mode:
+            self.log_std = nn.Parameter(torch.full((action_dim,), float(rc.logstd_init)))
+
+    def gru_slots(self) -> Dict[str, GRUNet]:
+        d = {}
+        if getattr(self, "shared_layers", None) is not None:
+            d["shared_h"] = self.shared_layers
+        if isinstance(self.actor, GRUNet):
+            d["actor_h"] = self.actor
+        if isinstance(self.critic, GRUNet):
+            d["critic_h"] = self.critic
+        return d
+
+    def step_rows(self, a_x, c_x, state, reset=None, group: int = 1, *, store: bool = True, out_state=None,
+                  actor: bool = True, critic: bool = True):
+        """One time step over rows: a_x / c_x [n, in] (the raw actor / critic observations), state
+        {slot: [n, layers, hidden]} -> (actor input [n, .] when the actor is an MLP else None, the
+        GRU actor's means [n, K] else None, values [n] or None, new state per slot -- None entries
+        with store False). Trunk, actor and critic run once each."""
+        out_state = out_state or {}
+        new: Dict[str, Optional[torch.Tensor]] = {}
+        a_in, c_in = a_x, c_x
+        if "shared_h" in state:
+            a_in, new["shared_h"] = self.shared_layers.step(a_x, state["shared_h"], reset, group, store_state=store,
+                                                            h_out=out_state.get("shared_h"))
+            c_in = a_in
+        mean = values = None
+        if "actor_h" in state and actor:
+            mean, new["actor_h"] = self.actor.step(a_in, state["actor_h"], reset, group, store_state=store,
+                                                   h_out=out_state.get("actor_h"))
+        if critic:
+            if "critic_h" in state:
+                values, new["critic_h"] = self.critic.step(c_in, state["critic_h"], reset, group, store_state=store,
+                                                           h_out=out_state.get("critic_h"))
+            else:
+                values = mlp_forward(self.critic, c_in)
+            values = values.squeeze(-1)
+        return (None if "actor_h" in state else a_in), mean, values, new
+
+    def sequence_rows(self, a_x, c_x, state_in, keep, logstd_floor: float):
+        """(mean [B, S, K], log_std, values [B, S]) of chunks a_x / c_x [B, S, in] from the states
+        state_in {slot: [B, layers, hidden]}; keep [B, S] (or None) multiplies the state entering
+        each step. The torch layers, with autograd as enabled (BPTT over the chunk)."""
+        a_in, c_in = a_x, c_x
+        if "shared_h" in state_in:
+            a_in, _ = self.shared_layers.sequence(a_x, state_in["shared_h"], keep)
+            c_in = a_in
+        if "actor_h" in state_in:
+            mean, _ = self.actor.sequence(a_in, state_in["actor_h"], keep)
+        elif self.head_mode:
+            mean, log_std = self.mu_sigma_head(self.actor(a_in))
+        else:
+            mean = self.actor(a_in)
+        if not self.head_mode:
+            log_std = torch.clamp(self.log_std, min=logstd_floor).expand_as(mean)
+        if "critic_h" in state_in:
+            values, _ = self.critic.sequence(c_in, state_in["critic_h"], keep)
+        else:
+            values = self.critic(c_in)
+        return mean, log_std, values.squeeze(-1)
+
+
+def recurrent_step(policies, shared: bool, rc: "RolloutConfig", local_obs, full_obs, state, reset=None, *,
+                   store: bool = True, out_state=None, actor: bool = True, critic: bool = True):
+    """PolicyNets.step_rows over [E, W, .] observations and {slot: [E, W, layers, hidden]} states for one
+    shared policy (all E W rows in one call, the reset flags [E] applying to groups of W rows) or W
+    per-agent policies. Returns (actor input [E, W, .] or None, means [E, W, K] or None, values
+    [E, W] or None, new state per slot)."""
+    a_x = full_obs if rc.actor_obs_type == "global" else local_obs
+    c_x = full_obs if rc.critic_obs_type == "global" else local_obs
+    E, W = local_obs.shape[0], local_obs.shape[1]
+    if shared:
+        flat = lambda t: None if t is None else t.reshape(E * W, *t.shape[2:])  # noqa: E731
+        a_in, mean, v, new = policies[0].step_rows(
+            flat(a_x), flat(c_x), {k: flat(h) for k, h in state.items()}, reset, W, store=store,
+            out_state={k: flat(h) for k, h in (out_state or {}).items()}, actor=actor, critic=critic)
+        un = lambda t: None if t is None else t.reshape(E, W, *t.shape[1:])  # noqa: E731
+        return un(a_in), un(mean), un(v), {k: un(h) for k, h in new.items()}
+    parts = [p.step_rows(a_x[:, w].contiguous(), c_x[:, w].contiguous(), {k: h[:, w].contiguous() for k, h in state.items()},
+                         reset, 1, store=store, actor=actor, critic=critic) for w, p in enumerate(policies)]
+    st = lambda i: None if parts[0][i] is None else torch.stack([q[i] for q in parts], dim=1)  # noqa: E731
+    new = {}
+    for k in state:
+        hs = [q[3].get(k) for q in parts]
+        new[k] = None if hs[0] is None else torch.stack(hs, dim=1)
+        if new[k] is not None and out_state and k in out_state:
+            new[k] = out_state[k].copy_(new[k])
+    return st(0), st(1), st(2), new
+
+
 # Inference (no autograd): a whole Linear-ReLU-Linear-ReLU-Linear MLP with hidden sizes 64 / 128 /
 # 256 (both actors, the IPPO critic) runs as one f32-MFMA kernel (marlsc/mlp.py, MSC_FUSED_MLP3=0
 # turns it off); any other Linear -> ReLU pair runs as one GEMM with the ReLU in the GEMM epilogue
@@ -174,10 +403,23 @@ class RolloutConfig:
     # networks.use_mu_sigma_head: the actor is a backbone under a MuSigmaHead (state-dependent
     # log_std; no free log_std parameter, logstd_init / logstd_floor unused)
     use_mu_sigma_head: bool = False
+    # networks.{actor,critic}.type ("mlp" or "gru") and networks.shared_layers.config of a gru trunk
+    # (None: no shared layers); max_seq_len is derived (the GRUs' common value, None without a GRU)
+    actor_type: str = "mlp"
+    critic_type: str = "mlp"
+    shared_layers: Optional[Dict[str, Any]] = None
+    max_seq_len: Optional[int] = None
+
+    def networks(self) -> Dict[str, Any]:
+        nets = {"use_mu_sigma_head": self.use_mu_sigma_head, "actor": {"type": self.actor_type, "config": self.actor},
+                "critic": {"type": self.critic_type, "config": self.critic}}
+        if self.shared_layers is not None:
+            nets["shared_layers"] = {"type": "gru", "config": self.shared_layers}
+        return nets
 
     def __post_init__(self):
-        check_head_config({"use_mu_sigma_head": self.use_mu_sigma_head, "actor": {"config": self.actor},
-                           "critic": {"config": self.critic}})
+        check_head_config(self.networks())
+        self.max_seq_len = check_gru_config(self.networks(), self.actor_obs_type, self.critic_obs_type)
 
     @classmethod
     def from_algorithm_config(cls, cfg: Dict[str, Any]) -> "RolloutConfig":
@@ -185,37 +427,87 @@ class RolloutConfig:
         a = cfg.get("algorithm", cfg)
         s = a.get("algorithm_specific", {})
         nets = s.get("networks", {}) or {}
-        if nets.get("shared_layers"):
-            raise ValueError("shared_layers (GRU) networks are outside this build's rollout path")
         head = check_head_config(nets)
-        for k in ("actor", "critic"):
-            if nets.get(k, {}).get("type", "mlp") != "mlp":
-                raise ValueError(f"{k}: only mlp networks are supported")
+        a_obs = s.get("actor_obs_type", "local")
+        c_obs = s.get("critic_obs_type", "global" if a.get("name") == "mappo" else "local")
+        check_gru_config(nets, a_obs, c_obs, (a.get("shared") or {}).get("batch_size"),
+                         (a.get("shared") or {}).get("num_minibatches"))
         return cls(gamma=float(s.get("gamma", 0.99)), lam=float(s.get("lam", 0.95)),
                    actor_obs_type=s.get("actor_obs_type", "local"),
                    critic_obs_type=s.get("critic_obs_type", "global" if a.get("name") == "mappo" else "local"),
                    logstd_init=float(s.get("logstd_init", -1.0)), logstd_floor=float(s.get("logstd_floor", -3.5)),
                    actor=(nets.get("actor") or {}).get("config"), critic=(nets.get("critic") or {}).get("config"),
-                   use_mu_sigma_head=head)
+                   use_mu_sigma_head=head, **network_types(nets))
 
 
-class ActorCritic(nn.Module):
+class RecurrentAPI:
+    """The collector's / learner's view of a module with GRU networks, over [E, W, .] tensors: needs
+    `_policy_list()` (one shared policy or W per-agent ones), `shared`, `rc` and `W`."""
+
+    @property
+    def recurrent(self) -> bool:
+        r = self.__dict__.get("_recurrent")  # (fixed at construction; asked on every stateless call)
+        if r is None:
+            r = self.__dict__["_recurrent"] = bool(self._policy_list()[0].gru_slots())
+        return r
+
+    @property
+    def max_seq_len(self) -> Optional[int]:
+        return self.rc.max_seq_len
+
+    def _stateless(self) -> None:
+        if self.recurrent:
+            raise ValueError("GRU networks carry state: use initial_state / step / sequence instead")
+
+    def initial_state(self, n: int, device=None) -> Dict[str, torch.Tensor]:
+        """Zeros [n, W, num_layers, hidden] per state slot (get_initial_state, rlmodules/base.py:351-388)."""
+        return {k: g.zero_state(n, self.W, device=device) for k, g in self._policy_list()[0].gru_slots().items()}
+
+    def step(self, local_obs, full_obs, state, reset=None, *, store: bool = True, out_state=None, actor: bool = True,
+             critic: bool = True):
+        """One time step taking and returning the state (see recurrent_step)."""
+        return recurrent_step(self._policy_list(), self.shared, self.rc, local_obs, full_obs, state, reset, store=store,
+                              out_state=out_state, actor=actor, critic=critic)
+
+    def sequence(self, local_obs, full_obs, state_in, keep=None):
+        """(mean, log_std, values) over [B, S, W, .] chunks from {slot: [B, W, layers, hidden]}; keep
+        [B, S] (1 - truncated of the previous step, 1 at s = 0) is shared by an env's agents."""
+        rc, ps = self.rc, self._policy_list()
+        a_x = full_obs if rc.actor_obs_type == "global" else local_obs
+        c_x = full_obs if rc.critic_obs_type == "global" else local_obs
+        outs = []
+        for w in range(local_obs.shape[2]):
+            p = ps[0] if self.shared else ps[w]
+            outs.append(p.sequence_rows(a_x[:, :, w], c_x[:, :, w], {k: h[:, w] for k, h in state_in.items()}, keep,
+                                        rc.logstd_floor))
+        return tuple(torch.stack([o[i] for o in outs], dim=2) for i in range(3))
+
+
+class ActorCritic(RecurrentAPI, PolicyNets, nn.Module):
+    shared = True
+
     def __init__(self, local_obs_dim: int, global_obs_dim: int, action_dim: int, rc: RolloutConfig):
         super().__init__()
         self.local_obs_dim, self.rc = local_obs_dim, rc
-        full = local_obs_dim + global_obs_dim
-        self.actor, head = build_actor(full if rc.actor_obs_type == "global" else local_obs_dim, action_dim, rc,
-                                       {"hidden_sizes": [256, 256]})
-        self.head_mode = head is not None
-        if self.head_mode:
-            self.mu_sigma_head = head
-        self.critic = MLP(full if rc.critic_obs_type == "global" else local_obs_dim, 1,
-                          rc.critic or {"hidden_sizes": [64, 64]})
-        if not self.head_mode:
-            self.log_std = nn.Parameter(torch.full((action_dim,), float(rc.logstd_init)))
+        self.W = max(1, global_obs_dim // max(1, local_obs_dim))
+        self._build_nets(local_obs_dim, global_obs_dim, action_dim, rc, {"hidden_sizes": [256, 256]},
+                         {"hidden_sizes": [64, 64]})
+
+    def _policy_list(self):
+        return [self]
+
+    def actor_sample_x(self, x: torch.Tensor, sample) -> bool:
+        return fused_actor_sample(self.actor, x, sample)
+
+    def sample_actions_x(self, x, eps, actions, logp) -> torch.Tensor:
+        return head_sample(self.actor, self.mu_sigma_head, x, eps, actions, logp)
+
+    def actor_mean_x(self, x: torch.Tensor) -> torch.Tensor:
+        return self.actor(x)
 
     def dist_inputs(self, local_obs: torch.Tensor, full_obs: Optional[torch.Tensor] = None):
         """(mean, log_std) -- ACTION_DIST_INPUTS split in two."""
+        self._stateless()
         if self.head_mode:  # the torch layer sequence (per-row log_std), with or without autograd
             return self.mu_sigma_head(self.actor(full_obs if self.rc.actor_obs_type == "global" else local_obs))
         mean = self.actor_mean(local_obs, full_obs)
@@ -246,6 +538,7 @@ class ActorCritic(nn.Module):
     def values(self, local_obs: torch.Tensor, full_obs: Optional[torch.Tensor] = None,
                out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """V [..., W]; `out` (contiguous, that shape) receives it when the fused critic runs."""
+        self._stateless()
         if self.rc.critic_obs_type == "global" and full_obs is None:
             return split_global_mlp(self.critic, local_obs, out=out).squeeze(-1)
         x = full_obs if self.rc.critic_obs_type == "global" else local_obs
@@ -459,6 +752,22 @@ class RolloutCollector:
         self._values_out = "out" in inspect.signature(module.values).parameters
         self._ls: Optional[torch.Tensor] = None
         self._head = bool(getattr(module, "head_mode", False))  # mu/sigma-head module (sample_actions)
+        # GRU networks: per-env state per slot ([E, W, layers, hidden], zero now, carried across
+        # collect() calls like the env's observation) in two buffers that the steps ping-pong, and the
+        # learner's state_in[slot] [T / S, E, W, layers, hidden]: the state entering steps 0, S, 2S, ...
+        self._recurrent = bool(getattr(module, "recurrent", False))
+        self.state_in: Dict[str, torch.Tensor] = {}
+        if self._recurrent:
+            S = int(module.max_seq_len)
+            if T % S != 0:
+                raise ValueError(f"rollout length T = {T} must be a multiple of max_seq_len = {S}")
+            self.S = S
+            self._hbuf = [module.initial_state(E, device=dev), module.initial_state(E, device=dev)]
+            self._hcur = 0
+            self.state_in = {k: torch.zeros((T // S,) + tuple(h.shape), device=dev) for k, h in self._hbuf[0].items()}
+            rc = module.rc
+            self._need_flat = "global" in (rc.actor_obs_type, rc.critic_obs_type)
+            self._critic_side = False  # the critic shares the trunk / carries state: on the chain
         # obs_normalization "meanstd": RLlib's running filter, one per lane (env runner), synchronised
         # after every collect (marlsc/obs_filter.py)
         self.obs_filter = None
@@ -508,28 +817,89 @@ class RolloutCollector:
             return max(1, int(os.environ["MSC_NOISE_CHUNK"]))
         return max(NOISE_CHUNK, min(self.T, (1 << 30) // per_step))
 
+    @property
+    def state(self) -> Dict[str, torch.Tensor]:
+        """The current recurrent state per slot ([E, W, layers, hidden]; empty without GRU networks)."""
+        return self._hbuf[self._hcur] if self._recurrent else {}
+
+    def load_state(self, state: Dict[str, torch.Tensor]) -> None:
+        for k, h in self.state.items():
+            h.copy_(state[k].to(h.device))
+
+    def _lane_noise(self, ln: _Lane, t: int, sl: slice) -> torch.Tensor:
+        """Step t's standard-normal noise of the lane, drawn for `chunk` steps at once (one launch instead
+        of one per step), keyed by global env id. The whole rollout's noise when it fits 1 GiB: a noise
+        launch between step_c and the actor lets the next demand kernel reach the CUs before the actor,
+        whose one 384-VGPR wave per SIMD then no longer fits beside the demand waves (the actor of
+        that step 378 -> 906 us, profiles/r06/trace_roll_c3_r06il.txt)."""
+        chunk = self._noise_chunk(ln)
+        if t % chunk == 0:
+            n = min(chunk, self.T - t)
+            shape = (n,) + tuple(self.actions[t, sl].shape)
+            if _TORCH_NOISE:  # A/B only: torch's generator (not shard-invariant)
+                dev = self.actions.device
+                if not hasattr(self, "_gen"):
+                    self._gen = torch.Generator(device=dev).manual_seed(self._noise_seed & 0x7FFFFFFF)
+                ln.noise = torch.randn(shape, device=dev, generator=self._gen)
+            else:
+                ln.noise = keyed_normal(shape, ln.env.env_index_offset, self._noise_seed, self.noise_step + t)
+        return ln.noise[t % chunk]
+
+    def _step_recurrent(self, ln: _Lane, t: int) -> None:
+        """_step for modules with GRU networks: trunk / actor / critic once each on obs_t from the lane's
+        state, with the reset flags of step t - 1 (an env's state is zero for the first observation of
+        a new episode); V(final_obs) from the state after step t, which it does not advance."""
+        env, m, sl = ln.env, self.module, slice(ln.e0, ln.e1)
+        obs = self._obs_all[t, sl]
+        full = self._full(ln, obs)
+        cur = {k: h[sl] for k, h in self._hbuf[self._hcur].items()}
+        nxt = {k: h[sl] for k, h in self._hbuf[self._hcur ^ 1].items()}
+        reset = self._trunc_env[t - 1, sl] if t > 0 else None  # (the last collect's flags were applied at its end)
+        if t % self.S == 0:  # the learner's chunk starts here: the state as the step reads it
+            if reset is not None:
+                keep = (reset == 0).to(torch.float32).view(-1, 1, 1, 1)
+                for h in cur.values():
+                    h.mul_(keep)
+                reset = None
+            for k, h in cur.items():
+                self.state_in[k][t // self.S, sl].copy_(h)
+        eps = self._lane_noise(ln, t, sl)
+        a_in, mean, v, _ = m.step(obs, full, cur, reset, out_state=nxt)
+        self.values[t, sl].copy_(v)
+        a = None
+        if mean is None:  # MLP actor on the trunk's features (or the raw observation): its fused paths
+            if self._head:
+                a = m.sample_actions_x(a_in, eps, self.actions[t, sl], self.logp[t, sl])
+            else:
+                clipped = torch.empty_like(self.actions[t, sl])
+                if m.actor_sample_x(a_in, (self._ls, m.rc.logstd_floor, eps, self.actions[t, sl], self.logp[t, sl],
+                                           clipped)):
+                    a = clipped
+                else:
+                    mean = m.actor_mean_x(a_in)
+        if a is None:
+            a = gaussian_sample(mean.contiguous(), self._ls, m.rc.logstd_floor, eps, self.actions[t, sl], self.logp[t, sl])
+        may_end = env.may_truncate()
+        _, _, trunc, final_obs = env.step(a, obs_out=self._obs_all[t + 1, sl], rewards_out=self.rewards[t, sl],
+                                          truncated_out=self._trunc_env[t, sl])
+        if self.obs_filter is not None:
+            li = self._lanes.index(ln)
+            self.obs_filter.apply(li, self._obs_all[t + 1, sl])
+            if may_end:
+                self.obs_filter.apply(li, final_obs, mask=trunc)
+        if may_end:  # RLlib's extra-timestep bootstrap: the state after step t, not advanced
+            _, _, vf, _ = m.step(final_obs, self._full(ln, final_obs), nxt, None, store=False, actor=False)
+            self.next_values[t, sl] = torch.where(trunc.bool().unsqueeze(-1), vf, torch.zeros((), device=vf.device))
+
     def _step(self, ln: _Lane, t: int) -> None:
+        if self._recurrent:
+            return self._step_recurrent(ln, t)
         env, m, sl = ln.env, self.module, slice(ln.e0, ln.e1)
         obs = self._obs_all[t, sl]
         full = self._full(ln, obs)
         if self._critic_side:
             self._critic_on_side(ln, t, sl, obs, full)
-        # standard-normal noise for `chunk` steps of the lane at once (one launch instead of one per
-        # step), keyed by global env id. The whole rollout's noise when it fits 1 GiB: a noise launch
-        # between step_c and the actor lets the next demand kernel reach the CUs before the actor,
-        # whose one 384-VGPR wave per SIMD then no longer fits beside the demand waves (the actor of
-        # that step 378 -> 906 us, profiles/r06/trace_roll_c3_r06il.txt)
-        chunk = self._noise_chunk(ln)
-        if t % chunk == 0:
-            n = min(chunk, self.T - t)
-            if _TORCH_NOISE:  # A/B only: torch's generator (not shard-invariant)
-                if not hasattr(self, "_gen"):
-                    self._gen = torch.Generator(device=obs.device).manual_seed(self._noise_seed & 0x7FFFFFFF)
-                ln.noise = torch.randn((n,) + tuple(self.actions[t, sl].shape), device=obs.device, generator=self._gen)
-            else:
-                ln.noise = keyed_normal((n,) + tuple(self.actions[t, sl].shape), ln.env.env_index_offset,
-                                        self._noise_seed, self.noise_step + t)
-        eps = ln.noise[t % chunk]
+        eps = self._lane_noise(ln, t, sl)
         a = None
         if self._head:  # state-dependent log_std: one row per row (head_sample)
             a = m.sample_actions(obs, full, eps, self.actions[t, sl], self.logp[t, sl])
@@ -603,10 +973,22 @@ class RolloutCollector:
             for ln in self._lanes:
                 with ln.ctx():
                     self._step(ln, t)
+            if self._recurrent:
+                self._hcur ^= 1
         for ln in self._lanes:
             with ln.ctx():
                 last = self._obs_all[T, ln.e0:ln.e1]
-                self.values[T, ln.e0:ln.e1] = m.values(last, self._full(ln, last))
+                if self._recurrent:
+                    # V(obs_T) as step T would compute it, state untouched; then the pending resets are
+                    # applied, so an env whose episode ended at the last step holds a zero state
+                    sl = slice(ln.e0, ln.e1)
+                    cur, reset = {k: h[sl] for k, h in self.state.items()}, self._trunc_env[T - 1, sl]
+                    self.values[T, sl] = m.step(last, self._full(ln, last), cur, reset, store=False, actor=False)[2]
+                    keep = (reset == 0).to(torch.float32).view(-1, 1, 1, 1)
+                    for h in cur.values():
+                        h.mul_(keep)
+                else:
+                    self.values[T, ln.e0:ln.e1] = m.values(last, self._full(ln, last))
                 ln.env.obs.copy_(last)  # the env's own buffer holds the current observation again
             if ln.stream is not None:
                 main.wait_stream(ln.stream)
@@ -624,5 +1006,8 @@ class RolloutCollector:
         if normalize:
             allreduce_adv_stats(self.stats)
             normalize_advantages(self.adv, self.stats)
-        return {"obs": self.obs, "actions": self.actions, "logp": self.logp, "rewards": self.rewards,
-                "values": self.values, "advantages": self.adv, "value_targets": self.targets}
+        out = {"obs": self.obs, "actions": self.actions, "logp": self.logp, "rewards": self.rewards,
+               "values": self.values, "advantages": self.adv, "value_targets": self.targets}
+        if self._recurrent:
+            out["state_in"], out["truncated"] = self.state_in, self.truncated
+        return out
