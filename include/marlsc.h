@@ -381,7 +381,22 @@ int msc_meanstd_filter(const float* obs, float* out, int64_t n_rows, int32_t n_c
  * f32 device buffers; stream-ordered. pre1 (optional, [n_rows / pre1_group][hidden1]) is added to
  * the first layer's pre-activation of every row n as pre1[n / pre1_group]: the MAPPO critic's
  * first layer over local_w || global (multi_env.py:566-573) is W_local x_w + (W_global g_env + b1),
- * with the global block computed once per env (pre1_group = agents). */
+ * with the global block computed once per env (pre1_group = agents). A partial last group is legal:
+ * pre1 then has ceil(n_rows / pre1_group) rows.
+ *
+ * Exactness. Every product (f32 MFMA, and the fma of the VALU output layer) is exact and every
+ * accumulation is float32, in an order that depends on the kernel form. So when x, the weights, the
+ * biases and pre1 hold integers and |b| (+ |pre1|) + sum_k |w_k| |h_k| < 2^24 at every layer, every
+ * partial sum is exact and the outputs equal the integer evaluation bit for bit, for every hidden-size
+ * branch, output-layer form (msc_mlp3_w3_layout) and MSC_MLP_P8 pass form; tests/test_gpu_mlp_exact.py
+ * holds all of them to that. For general inputs the result is one float32 rounding order among many
+ * (its error against float64 was measured at 0.5 to 0.9 of a CPU float32 evaluation's).
+ * Rows are independent: a row's outputs depend on its own in_dim inputs (and its pre1 row) only, and
+ * do not change with its position in the batch.
+ * Non-finite inputs. A row of x that holds NaN or +-Inf leaves every other row's outputs bit-identical.
+ * What that row itself returns is unspecified: the ReLU is fmaxf(h, 0), which maps a NaN hidden unit to
+ * 0 where torch's relu returns NaN, so the row may come back finite. The same holds for
+ * msc_mlp2_relu_forward, the _sampled entry points and msc_mlp{2,3}_relu_musigma below. */
 int msc_mlp3_w3_layout(int32_t out_dim);
 int msc_mlp3_relu_forward(const float* x, int64_t n_rows, int32_t in_dim, int32_t hidden1, int32_t hidden2,
                           int32_t out_dim, const float* w1p, const float* b1, const float* w2p, const float* b2,
