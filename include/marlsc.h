@@ -438,6 +438,40 @@ int msc_mlp2_relu_forward_sampled(const float* x, int64_t n_rows, int32_t in_dim
                                   const float* pre1, int32_t pre1_group, const msc_gaussian_epilogue* sample,
                                   msc_stream_t stream);
 
+/* Wide-output policy inference: the centralised (CPPO) actor maps the global observation to the joint
+ * action, n_warehouses * L -> hidden -> n_warehouses * n_skus (the reference's src/algorithms/cppo.py
+ * builds it with MLPArchitecture.build, architectures/mlp.py:14-60; 40 outputs at C3, 80 at C5).
+ * Replaces, for 1 <= out_dim <= 128, the actor's torch layer sequence in _forward_inference and, with
+ * `sample`, the TorchDiagGaussian sample after it (rlmodules/base.py:480-557): the same networks,
+ * in_dim, pre1 / pre1_group and exactness / row-independence / non-finite-row statements as
+ * msc_mlp3_relu_forward and msc_mlp2_relu_forward, with the output layer on ceil(out_dim / 32) <= 4
+ * MFMA tiles. w1p / w2p as there; w3p [ceil(out_dim/32)][hidden_last/8][64][4]: the layout-0 (MFMA)
+ * fragment order of msc_mlp3_relu_forward once per 32-row slice of W3, slices concatenated, rows past
+ * out_dim zero (marlsc/mlp.py:pack_wide).
+ * sample may be NULL (means only, out required); with it, out may be NULL. actions and clipped are
+ * msc_gaussian_sample's, operation for operation, and logp adds the row's out_dim terms sequentially
+ * in k from 0.0f as that kernel does, so all three are bit-identical to msc_gaussian_sample run on
+ * the means. Nothing is read or written past n_rows rows or out_dim columns; n_rows = 0 launches nothing.
+ * msc_mlp_wide_supported(hidden1, hidden2 (0: one hidden layer), out_dim): 1 when a wide kernel
+ * exists (hidden sizes as the narrow kernels', 1 <= out_dim <= 128), else 0; the entry points return
+ * an error, without a launch, for anything else. */
+int msc_mlp_wide_supported(int32_t hidden1, int32_t hidden2, int32_t out_dim);
+int msc_mlp3_relu_wide(const float* x, int64_t n_rows, int32_t in_dim, int32_t hidden1, int32_t hidden2,
+                       int32_t out_dim, const float* w1p, const float* b1, const float* w2p, const float* b2,
+                       const float* w3p, const float* b3, float* out, const float* pre1, int32_t pre1_group,
+                       const msc_gaussian_epilogue* sample, msc_stream_t stream);
+int msc_mlp2_relu_wide(const float* x, int64_t n_rows, int32_t in_dim, int32_t hidden, int32_t out_dim,
+                       const float* w1p, const float* b1, const float* w3p, const float* b3, float* out,
+                       const float* pre1, int32_t pre1_group, const msc_gaussian_epilogue* sample,
+                       msc_stream_t stream);
+
+/* Team reward of the centralised view: replaces the reference wrapper's sum(rewards.values())
+ * (src/environment/envs/single_env.py:156). rewards [n_envs][n_agents] f64 (device); per env the
+ * agent-order sum ((r0 + r1) + r2) ... in f64 to out64 [n_envs] and, rounded once, to out32 [n_envs]
+ * (either may be NULL, not both). One launch. */
+int msc_reward_team_sum(const double* rewards, int64_t n_envs, int32_t n_agents, float* out32, double* out64,
+                        msc_stream_t stream);
+
 /* Rollout inference of a mu / sigma-head actor (use_mu_sigma_head): replaces the torch layer sequence
  * backbone -> MuSigmaHead.forward (architectures/mu_sigma_head.py:52-82, wired in
  * rlmodules/base.py:434-435) and, with the sampling buffers, the EnvRunner's TorchDiagGaussian

@@ -1503,6 +1503,67 @@ int msc_mlp2_relu_forward_sampled(const float* x, int64_t n_rows, int32_t in_dim
   return mlp2_impl(x, n_rows, in_dim, hidden, out_dim, w1p, b1, w3p, b3, out, pre1, pre1_group, sample, stream);
 }
 
+// wide-output MLPs (the centralised actor, cppo.py: MLPArchitecture.build over the global observation
+// to the joint action): multi-tile MFMA output layer, optional LDS-staged sampling epilogue
+int msc_mlp_wide_supported(int32_t hidden1, int32_t hidden2, int32_t out_dim) {
+  return mlp_wide_supported(hidden1, hidden2, out_dim) ? 1 : 0;
+}
+
+static int mlp_wide_impl(const float* x, int64_t n_rows, int32_t in_dim, int32_t hidden1, int32_t hidden2,
+                         int32_t out_dim, const float* w1p, const float* b1, const float* w2p, const float* b2,
+                         const float* w3p, const float* b3, float* out, const float* pre1, int32_t pre1_group,
+                         const msc_gaussian_epilogue* g, msc_stream_t stream) {
+  const bool two = hidden2 != 0;
+  if (pre1 && pre1_group < 1) return set_err(-1, "pre1_group %d must be >= 1", pre1_group);
+  if (((uintptr_t)b1 | (uintptr_t)b2 | (uintptr_t)pre1 | (uintptr_t)w1p | (uintptr_t)w2p | (uintptr_t)w3p) & 15)
+    return set_err(-1, "b1, b2, pre1 and the packed weights must be 16-byte aligned");
+  if (!x || !w1p || !b1 || (two && (!w2p || !b2)) || !w3p || !b3 || (!out && !g)) return set_err(-1, "null argument");
+  if (n_rows < 0 || in_dim < 1 || in_dim > 1024 || out_dim < 1 || out_dim > 128)
+    return set_err(-1, "bad shape (n_rows %lld, in_dim %d, out_dim %d)", (long long)n_rows, in_dim, out_dim);
+  if (!mlp_wide_supported(hidden1, hidden2, out_dim))
+    return two ? set_err(-1, "hidden sizes %d, %d: the wide MLP supports [H1, H2] with H1, H2 in {64, 128, 256, 512}", hidden1, hidden2)
+               : set_err(-1, "hidden size %d: the wide MLP supports multiples of 32 up to 1024", hidden1);
+  MlpSample sm{};
+  if (g) {
+    if (!g->log_std || !g->eps || !g->actions || !g->logp || !g->clipped) return set_err(-1, "null sampling buffer");
+    if (g->log_std_rows < 1) return set_err(-1, "log_std_rows %d must be >= 1", g->log_std_rows);
+    sm = MlpSample{g->log_std, g->log_std_rows, g->logstd_floor, g->eps, g->actions, g->logp, g->clipped};
+  }
+  if (two)
+    HIP_TRY(launch_mlp3_wide(x, n_rows, in_dim, hidden1, hidden2, out_dim, w1p, b1, w2p, b2, w3p, b3, out, pre1,
+                             pre1 ? pre1_group : 1, (hipStream_t)stream, g ? &sm : nullptr));
+  else
+    HIP_TRY(launch_mlp2_wide(x, n_rows, in_dim, hidden1, out_dim, w1p, b1, w3p, b3, out, pre1, pre1 ? pre1_group : 1,
+                             (hipStream_t)stream, g ? &sm : nullptr));
+  return 0;
+}
+
+int msc_mlp3_relu_wide(const float* x, int64_t n_rows, int32_t in_dim, int32_t hidden1, int32_t hidden2,
+                       int32_t out_dim, const float* w1p, const float* b1, const float* w2p, const float* b2,
+                       const float* w3p, const float* b3, float* out, const float* pre1, int32_t pre1_group,
+                       const msc_gaussian_epilogue* sample, msc_stream_t stream) {
+  if (hidden2 == 0) return set_err(-1, "hidden2 must be one of {64, 128, 256, 512} (one hidden layer: msc_mlp2_relu_wide)");
+  return mlp_wide_impl(x, n_rows, in_dim, hidden1, hidden2, out_dim, w1p, b1, w2p, b2, w3p, b3, out, pre1, pre1_group,
+                       sample, stream);
+}
+
+int msc_mlp2_relu_wide(const float* x, int64_t n_rows, int32_t in_dim, int32_t hidden, int32_t out_dim,
+                       const float* w1p, const float* b1, const float* w3p, const float* b3, float* out,
+                       const float* pre1, int32_t pre1_group, const msc_gaussian_epilogue* sample,
+                       msc_stream_t stream) {
+  return mlp_wide_impl(x, n_rows, in_dim, hidden, 0, out_dim, w1p, b1, nullptr, nullptr, w3p, b3, out, pre1, pre1_group,
+                       sample, stream);
+}
+
+// replaces the centralised wrapper's sum(rewards.values()) (src/environment/envs/single_env.py:156)
+int msc_reward_team_sum(const double* rewards, int64_t n_envs, int32_t n_agents, float* out32, double* out64,
+                        msc_stream_t stream) {
+  if (!rewards || (!out32 && !out64)) return set_err(-1, "null argument");
+  if (n_envs < 0 || n_agents < 1) return set_err(-1, "bad shape (n_envs %lld, n_agents %d)", (long long)n_envs, n_agents);
+  HIP_TRY(launch_reward_team_sum(rewards, n_envs, n_agents, out32, out64, (hipStream_t)stream));
+  return 0;
+}
+
 // mu / sigma-head actors (replaces backbone -> MuSigmaHead.forward, mu_sigma_head.py:52-82, wired in
 // rlmodules/base.py:434-435, and the sampling of rlmodules/base.py:480-557)
 int msc_mlp_musigma_layout(int32_t hidden1, int32_t hidden2, int32_t k, int32_t* width, int32_t* stride) {

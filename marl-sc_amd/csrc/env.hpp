@@ -255,7 +255,17 @@ hipError_t launch_mlp2_relu(const float* x, int64_t n, int L, int H1, int KO, co
                             const float* w3p, const float* b3, float* out, const float* pre1, int grp, hipStream_t st,
                             const MlpSample* smp = nullptr);
 bool mlp2_supported(int H1);
-int mlp_p8();    // MSC_MLP_P8: the A/B form of the [256, 256] kernel (mlp.hip)
+// mlp_wide.hip: the multi-tile MFMA output layer (out_dim <= 128) with the LDS-staged sampling epilogue
+bool mlp_wide_supported(int H1, int H2, int KO);  // H2 = 0: one hidden layer
+hipError_t launch_mlp3_wide(const float* x, int64_t n, int L, int H1, int H2, int KO, const float* w1p, const float* b1,
+                            const float* w2p, const float* b2, const float* w3p, const float* b3, float* out,
+                            const float* pre1, int grp, hipStream_t st, const MlpSample* smp);
+hipError_t launch_mlp2_wide(const float* x, int64_t n, int L, int H1, int KO, const float* w1p, const float* b1,
+                            const float* w3p, const float* b3, float* out, const float* pre1, int grp, hipStream_t st,
+                            const MlpSample* smp);
+// gae.hip: out[e] = ((r[e][0] + r[e][1]) + ...) in f64 (out64) and rounded once to f32 (out32)
+hipError_t launch_reward_team_sum(const double* r, int64_t E, int32_t W, float* out32, double* out64, hipStream_t st);
+int mlp_p8();   // MSC_MLP_P8: the A/B form of the [256, 256] kernel (mlp.hip)
 int mlp_prio();  // MSC_MLP_PRIO
 // the fused MLPs' mu / sigma head epilogue (msc_musigma_epilogue): activations (MSC_ACT_* codes), the
 // log_std clamp, the optional store of [mu || log_std] and the optional sampling (act == nullptr: none)

@@ -288,6 +288,26 @@ hipError_t launch_gauss_sample(const float* mean, const float* log_std, int32_t 
   return hipGetLastError();
 }
 
+// Team reward of the centralised (CPPO) view: the reference wrapper's sum(rewards.values())
+// (src/environment/envs/single_env.py:156), i.e. Python's left-to-right float sum in agent order,
+// ((r0 + r1) + r2) ..., one lane per env; the f64 total and its single rounding to f32.
+__global__ __launch_bounds__(256) void reward_team_sum_kernel(const double* __restrict__ r, int64_t E, int32_t W,
+                                                              float* __restrict__ out32, double* __restrict__ out64) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= E) return;
+  const double* re = r + e * W;
+  double s = re[0];
+  for (int w = 1; w < W; w++) s += re[w];
+  if (out64) out64[e] = s;
+  if (out32) out32[e] = (float)s;
+}
+
+hipError_t launch_reward_team_sum(const double* r, int64_t E, int32_t W, float* out32, double* out64, hipStream_t st) {
+  if (E == 0) return hipSuccess;
+  hipLaunchKernelGGL(reward_team_sum_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, st, r, E, W, out32, out64);
+  return hipGetLastError();
+}
+
 // Rollout noise keyed by global env id: out[s][row][j] = N(0, 1) from Philox4x32-10 with key =
 // seed and counter = {j / 2, global row (= row0 + row, 64 bit), step0 + s}, Box-Muller on two 32-bit
 // uniforms giving elements j (cos) and j + 1 (sin). Every value depends only on (seed, global env id,

@@ -14,6 +14,7 @@ __all__ = [
     "ConfigNode", "load_environment_config", "load_feature_config", "validate_environment_config",
     "SeedManager", "default_train_seed", "EnvSpec", "make_synthetic_env_config",
     "VecInventoryEnv", "InventoryEnvironment", "CentralizedEnvWrapper", "VecCentralizedEnv",
+    "CPPOConfig", "CPPOTrainer", "CentralizedRolloutEnv", "CentralizedActorCritic",
 ]
 
 
@@ -27,4 +28,7 @@ def __getattr__(name):  # torch-dependent modules load lazily
     if name in ("CentralizedEnvWrapper", "VecCentralizedEnv"):
         from . import single_env
         return getattr(single_env, name)
+    if name in ("CPPOConfig", "CPPOTrainer", "CentralizedRolloutEnv", "CentralizedActorCritic"):
+        from . import cppo
+        return getattr(cppo, name)
     raise AttributeError(name)

@@ -1,5 +1,5 @@
 """CLI of the reference's experiment entry point (src/experiments/run_experiment.py), for the modes
-that drive this build's training path: `single` (train one seed, with periodic evaluation and
+that drive this build's training path (IPPO, MAPPO and CPPO algorithm configs): `single` (train one seed, with periodic evaluation and
 checkpoints) and `evaluate` (deterministic episodes from a checkpoint). Ray Tune sweeps, seed
 evaluation and W&B are out of scope; their flags are accepted and ignored.
 
@@ -115,14 +115,14 @@ def load_and_truncate_training_metrics(out: Path, completed: int):
 
 def _load_configs(env_path: str, algo_path: str):
     from .config import load_environment_config
-    from .ppo import PPOConfig
+    from .cppo import config_from_algorithm_config
     env_cfg = load_environment_config(env_path, allow_nr_ne_nw=True)
     algo_raw = yaml.safe_load(open(algo_path))
-    return env_cfg, algo_raw, PPOConfig.from_algorithm_config(algo_raw)
+    return env_cfg, algo_raw, config_from_algorithm_config(algo_raw)  # PPOConfig, or CPPOConfig for cppo
 
 
 def run_single(args) -> Dict[str, Any]:
-    from .ppo import PPOTrainer
+    from .cppo import trainer_class
     rank, world, local = _dist_setup()
     device = local if args.device is None else args.device
     if not args.env_config or not args.algorithm_config:
@@ -133,7 +133,7 @@ def run_single(args) -> Dict[str, Any]:
     root_seed = 42 if args.root_seed is None else args.root_seed
     name = args.experiment_name or f"{cfg.name.upper()}_{Path(args.env_config).stem}_seed{root_seed}"
     out = Path(args.storage_dir) / name
-    trainer = PPOTrainer(env_cfg, cfg, root_seed=root_seed, n_envs=args.envs, rollout_len=args.rollout_len,
+    trainer = trainer_class(cfg)(env_cfg, cfg, root_seed=root_seed, n_envs=args.envs, rollout_len=args.rollout_len,
                          device=device, eval_seed=args.eval_seed)
     metrics: List[Dict[str, Any]] = []
     best, best_it = float("-inf"), None
@@ -225,7 +225,7 @@ def _barrier(world: int) -> None:
 
 
 def run_evaluate(args) -> Dict[str, Any]:
-    from .ppo import PPOTrainer
+    from .cppo import trainer_class
     if not args.experiment_name:
         raise SystemExit("--experiment-name is required for --mode evaluate")
     out = Path(args.storage_dir) / args.experiment_name
@@ -240,7 +240,7 @@ def run_evaluate(args) -> Dict[str, Any]:
         env_meta["obs_stats"] = (np.asarray(state["obs_stats"][0], np.float32), np.asarray(state["obs_stats"][1], np.float32))
     root_seed = meta["root_seed"] if args.root_seed is None else args.root_seed
     # the smallest rollout the trainer accepts (one chunk of max_seq_len steps with GRU networks); unused
-    trainer = PPOTrainer(env_cfg, cfg, root_seed=root_seed, n_envs=1, rollout_len=cfg.rollout_config().max_seq_len or 1,
+    trainer = trainer_class(cfg)(env_cfg, cfg, root_seed=root_seed, n_envs=1, rollout_len=cfg.rollout_config().max_seq_len or 1,
                          device=0 if args.device is None else args.device, env_meta=env_meta, eval_seed=args.eval_seed)
     trainer.load_checkpoint(ckpt, runtime=False)  # weights only: evaluation builds its own envs
     n = args.eval_episodes or DEFAULT_EVAL_EPISODES

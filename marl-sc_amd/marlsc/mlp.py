@@ -15,8 +15,9 @@ learner's updates are picked up and the pack is rebuilt at most once per optimiz
 built on one HIP stream and used on another is ordered by an event (rollout lanes).
 
 Actors with the reference's mu/sigma head (`use_mu_sigma_head`) run through the same kernels with a
-dual-head output layer (msc_mlp{2,3}_relu_musigma, csrc/mlp_musigma.hip): see the section at the
-end of this file.
+dual-head output layer (msc_mlp{2,3}_relu_musigma, csrc/mlp_musigma.hip), and networks with 33..128
+outputs (the centralised CPPO actor) have a multi-tile output layer with its own sampling epilogue
+(msc_mlp{2,3}_relu_wide, csrc/mlp_wide.hip): see the sections at the end of this file.
 
 There is no CPU fallback: a CUDA tensor on a build without libmarlsc raises (abi.lib()).
 """
@@ -454,3 +455,114 @@ def musigma_folded(mods, head, x: torch.Tensor):
     if head.sigma_activation is not None:
         ls = head.sigma_activation(ls)
     return mu.reshape(*lead, K), torch.clamp(ls, LOG_STD_MIN, LOG_STD_MAX).reshape(*lead, K)
+
+
+# ----------------------------------------------------------------------------------------------
+# Wide-output MLPs (33..128 outputs: the centralised CPPO actor's joint action, W K = 40 at C3 and
+# 80 at C5): msc_mlp{2,3}_relu_wide (csrc/mlp_wide.hip), the output layer on ceil(KO / 32) MFMA tiles
+# and msc_gaussian_sample's arithmetic in an LDS-staged epilogue. Taken only where no kernel above
+# applies (KO > 32): every narrower network keeps the path it had. Opt-in at rollout (WIDE_ENABLED).
+# ----------------------------------------------------------------------------------------------
+WIDE_MAX_OUT = 128
+# The rollout dispatch (rollout.fused_actor_sample / mlp_forward) takes the wide kernel only with
+# MSC_WIDE_MLP=1: measured against the torch layers + msc_gaussian_sample it is 1.27x faster at the C3
+# shape (32,768 rows of 208 -> 256 -> 40) and 0.92x at the C5 shape (8,192 rows of 416 -> 256 -> 80: 256
+# waves of 32 rows on 1,024 SIMDs), and the default needs both.
+# wide_forward itself does not look at the switch.
+WIDE_ENABLED = os.environ.get("MSC_WIDE_MLP", "0") == "1"
+
+
+def _wide_index(H: int, KO: int, device):
+    """w3p[o][q][lane][i] = W3[32 o + c][32 (q // 4) + rho(4 (q % 4) + i, h)] (0 for rows >= KO): the
+    layout-0 fragment order of _index_maps once per 32-row slice of W3, slices concatenated."""
+    key = ("wide", H, KO, str(device))
+    if key not in _IDX:
+        lane = torch.arange(64, device=device)
+        c, h = (lane & 31)[None, None, :, None], (lane >> 5)[None, None, :, None]
+        NTO = (KO + 31) // 32
+        o = torch.arange(NTO, device=device)[:, None, None, None]
+        q = torch.arange((H // 32) * 4, device=device)[None, :, None, None]
+        r = (q % 4) * 4 + torch.arange(4, device=device)[None, None, None, :]
+        row = o * 32 + c
+        idx = (row.clamp(max=KO - 1) * H + (q // 4) * 32 + _rho(r, h)).reshape(-1)
+        _IDX[key] = (idx, (row < KO).expand(NTO, (H // 32) * 4, 64, 4).reshape(-1))
+    return _IDX[key]
+
+
+def pack_wide(w1: torch.Tensor, w2: Optional[torch.Tensor], w3: torch.Tensor):
+    """Torch Linear weights -> (w1p, w2p, w3p) for msc_mlp{2,3}_relu_wide: w1p / w2p as pack_mlp3's,
+    w3p [ceil(KO / 32)][H_last / 8][64][4] (see _wide_index). w2 None: one hidden layer."""
+    H1, L = w1.shape
+    H2, KO = (w2.shape[0] if w2 is not None else 0), w3.shape[0]
+    if not 1 <= KO <= WIDE_MAX_OUT:
+        raise ValueError(f"the wide MLP supports 1..{WIDE_MAX_OUT} outputs, not {KO}")
+    i1, v1, i2, _, _ = _index_maps(L, H1, H2, min(KO, MAX_OUT), w1.device, 0)
+    i3, v3 = _wide_index(H2 or H1, KO, w1.device)
+    zero = torch.zeros((), device=w1.device, dtype=torch.float32)
+    w1p = torch.where(v1, w1.detach().float().reshape(-1)[i1], zero)
+    w2p = w2.detach().float().reshape(-1)[i2].contiguous() if w2 is not None else None
+    w3p = torch.where(v3, w3.detach().float().reshape(-1)[i3], zero)
+    return w1p.contiguous(), w2p, w3p.contiguous()
+
+
+def wide_layers(mods) -> int:
+    """2 or 3 when mods has a wide kernel: fused_layers' Linear / ReLU / bias / hidden-size
+    conditions with 32 < out_dim <= 128; 0 otherwise."""
+    if not mods or not isinstance(mods[-1], nn.Linear) or not MAX_OUT < mods[-1].out_features <= WIDE_MAX_OUT:
+        return 0
+    return fused_layers(mods, max_out=WIDE_MAX_OUT)
+
+
+def wide_forward(mods, x: torch.Tensor, out: Optional[torch.Tensor] = None, *, sample=None,
+                 w1: Optional[torch.Tensor] = None, pre1: Optional[torch.Tensor] = None, group: int = 1):
+    """msc_mlp{2,3}_relu_wide over x [..., L] (f32 CUDA) -> [..., KO]; wide_layers(mods) must hold.
+    sample: (log_std [P, KO], logstd_floor, eps, actions, logp, clipped) -- msc_gaussian_sample's
+    arithmetic in the kernel's epilogue, bit-identical to the separate call on the means; the means
+    then go to `out` only when it is given (returns `out`, possibly None). w1 / pre1 / group as in
+    mlp3_forward."""
+    nl = wide_layers(mods)
+    if nl == 0:
+        raise ValueError("no wide kernel for this layer sequence (see wide_layers)")
+    l1, l3 = mods[0], mods[-1]
+    l2 = mods[2] if nl == 3 else None
+    w1 = l1.weight if w1 is None else w1
+    L, KO = w1.shape[1], l3.out_features
+    if x.shape[-1] != L:
+        raise ValueError(f"input has {x.shape[-1]} features, the MLP expects {L}")
+    cur = torch.cuda.current_stream(x.device)
+    weights = (w1, l3.weight) if l2 is None else (w1, l2.weight, l3.weight)
+    w1p, w2p, w3p = _cached_pack(l1, ("wide", w1.shape, w1.stride(), w1.storage_offset()), weights, cur,
+                                 lambda: pack_wide(w1, None if l2 is None else l2.weight, l3.weight))
+    lead, xf = x.shape[:-1], _rows(x, L)
+    n = xf.shape[0]
+    if pre1 is not None:
+        pre1 = pre1.float().contiguous()
+        if group < 1 or n % group or pre1.shape != (n // group, l1.out_features):
+            raise ValueError(f"pre1 must be [{n // max(group, 1)}, {l1.out_features}] for {n} rows in groups of {group}")
+    vp = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+    ep = None
+    if sample is not None:
+        ls, floor, eps, act, logp, clipped = sample
+        for t in (ls, eps, act, logp, clipped):
+            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+                raise ValueError("sampling buffers must be contiguous float32 CUDA tensors")
+        if eps.numel() != n * KO or act.numel() != n * KO or clipped.numel() != n * KO or logp.numel() != n \
+                or ls.dim() != 2 or ls.shape[1] != KO:
+            raise ValueError("sampling buffers do not match the MLP's rows / outputs")
+        ep = C.byref(abi.MscGaussianEpilogue(vp(ls), int(ls.shape[0]), C.c_float(floor), vp(eps), vp(act), vp(logp),
+                                             vp(clipped)))
+    elif out is None:
+        out = torch.empty((n, KO), device=x.device, dtype=torch.float32)
+    if out is not None and not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
+                                and out.numel() == n * KO):
+        raise ValueError("out must be a contiguous float32 CUDA tensor of rows x outputs")
+    st = C.c_void_p(cur.cuda_stream)
+    b1, b3 = (m.bias.detach().float().contiguous() for m in (l1, l3))
+    if l2 is None:
+        abi.check(abi.lib().msc_mlp2_relu_wide(vp(xf), n, L, l1.out_features, KO, vp(w1p), vp(b1), vp(w3p), vp(b3),
+                                               vp(out), vp(pre1), int(group), ep, st))
+    else:
+        b2 = l2.bias.detach().float().contiguous()
+        abi.check(abi.lib().msc_mlp3_relu_wide(vp(xf), n, L, l1.out_features, l2.out_features, KO, vp(w1p), vp(b1),
+                                               vp(w2p), vp(b2), vp(w3p), vp(b3), vp(out), vp(pre1), int(group), ep, st))
+    return None if out is None else out.reshape(*lead, KO)

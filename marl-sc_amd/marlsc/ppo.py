@@ -95,12 +95,14 @@ class PPOConfig:
     critic_obs_type: str = "local"
     networks: Dict[str, Any] = field(default_factory=dict)
 
+    _NAMES = ("ippo", "mappo")  # the algorithm names this config class reads (cppo: marlsc/cppo.py:CPPOConfig)
+
     @classmethod
     def from_algorithm_config(cls, cfg: Dict[str, Any]) -> "PPOConfig":
         a = cfg.get("algorithm", cfg)
-        name = str(a.get("name", "ippo")).lower()
-        if name not in ("ippo", "mappo"):
-            raise ValueError(f"algorithm '{name}': this build trains ippo and mappo")
+        name = str(a.get("name", cls._NAMES[0])).lower()
+        if name not in cls._NAMES:
+            raise ValueError(f"algorithm '{name}': {cls.__name__} reads {' and '.join(cls._NAMES)}")
         sh = dict(a.get("shared", {}) or {})
         sp = dict(a.get("algorithm_specific", {}) or {})
         known = {f for f in cls.__dataclass_fields__}
@@ -609,7 +611,7 @@ class PPOTrainer:
         self.train_seed = self.sm.get_seed_int("train")
         self.eval_seed = eval_seed if eval_seed is not None else self.sm.get_seed_int("eval")
         meta = dict(env_meta or {})
-        meta["include_warehouse_id"] = bool(cfg.parameter_sharing)
+        meta["include_warehouse_id"] = self._include_warehouse_id()
         meta["obs_normalization"] = cfg.obs_normalization
         if cfg.obs_normalization in ("meanstd_custom", "meanstd_grouped") and meta.get("obs_stats") is None:
             meta["obs_stats"] = compute_obs_statistics(env_config, self.sm, cfg.obs_normalization, n_episodes=100,
@@ -630,12 +632,12 @@ class PPOTrainer:
         self.device = torch.device("cuda", device)
         # weak partition: rank g steps global env ids [g E, (g + 1) E); ranks sharing a device split
         # the episode-ahead memory budget
-        self.env = VecInventoryEnv(None, E, spec=self.spec, device=device, base_seed=self.train_seed,
-                                   env_index_offset=mdist.shard(E, "weak", self.rank, self.world)[1],
-                                   ea_mem_fraction=mdist.ea_mem_fraction())
+        self.env = self._wrap_env(VecInventoryEnv(None, E, spec=self.spec, device=device, base_seed=self.train_seed,
+                                                  env_index_offset=mdist.shard(E, "weak", self.rank, self.world)[1],
+                                                  ea_mem_fraction=mdist.ea_mem_fraction()))
         torch.manual_seed(self.train_seed)
-        W, L = self.env.W, self.env.local_obs_dim
-        self.module = MultiAgentActorCritic(W, L, L * W, self.env.K, rc, cfg.parameter_sharing).to(self.device)
+        W = self.env.W
+        self.module = self._build_module(rc).to(self.device)
         if self.world > 1:  # identical initial weights on every rank
             for p in self.module.parameters():
                 dist.broadcast(p.data, src=0)
@@ -654,6 +656,18 @@ class PPOTrainer:
         # return is the mean of the last num_eval_episodes completed episodes
         self._completed: deque = deque(maxlen=max(1, int(cfg.num_eval_episodes)))
         self._n_episodes = 0
+
+    # -- what a trainer over another view of the env overrides (marlsc/cppo.py:CPPOTrainer) --
+    def _include_warehouse_id(self) -> bool:
+        return bool(self.cfg.parameter_sharing)
+
+    def _wrap_env(self, env):
+        """The env as the collector / evaluation steps it (the training env and every evaluation env)."""
+        return env
+
+    def _build_module(self, rc: RolloutConfig) -> MultiAgentActorCritic:
+        W, L = self.env.W, self.env.local_obs_dim
+        return MultiAgentActorCritic(W, L, L * W, self.env.K, rc, self.cfg.parameter_sharing)
 
     def _full_fn(self):
         if self.cfg.actor_obs_type != "global" and not (self.module.recurrent and self.cfg.critic_obs_type == "global"):
@@ -729,8 +743,8 @@ class PPOTrainer:
         meta["num_eval_episodes"] = n
         spec = EnvSpec.from_config(self.env_config, meta)
         root = self.eval_seed if seed is None else int(seed)
-        env = VecInventoryEnv(None, n, spec=spec, device=self.device.index,
-                              env_seeds=np.full(n, root & 0xFFFFFFFF, dtype=np.uint32), episode_ahead=0)
+        env = self._wrap_env(VecInventoryEnv(None, n, spec=spec, device=self.device.index,
+                                             env_seeds=np.full(n, root & 0xFFFFFFFF, dtype=np.uint32), episode_ahead=0))
         env.set_episode_counters(np.arange(n, dtype=np.int32))
         obs = env.reset()
         full_fn = self._full_fn()

@@ -339,7 +339,9 @@ def recurrent_step(policies, shared: bool, rc: "RolloutConfig", local_obs, full_
             out_state={k: flat(h) for k, h in (out_state or {}).items()}, actor=actor, critic=critic)
         un = lambda t: None if t is None else t.reshape(E, W, *t.shape[1:])  # noqa: E731
         return un(a_in), un(mean), un(v), {k: un(h) for k, h in new.items()}
-    parts = [p.step_rows(a_x[:, w].contiguous(), c_x[:, w].contiguous(), {k: h[:, w].contiguous() for k, h in state.items()},
+    # (a slot is None once a step skipped its network, e.g. the critic's in evaluation: as the shared path takes it)
+    parts = [p.step_rows(a_x[:, w].contiguous(), c_x[:, w].contiguous(),
+                         {k: None if h is None else h[:, w].contiguous() for k, h in state.items()},
                          reset, 1, store=store, actor=actor, critic=critic) for w, p in enumerate(policies)]
     st = lambda i: None if parts[0][i] is None else torch.stack([q[i] for q in parts], dim=1)  # noqa: E731
     new = {}
@@ -377,6 +379,10 @@ def mlp_forward(layers, x: torch.Tensor, start: int = 0, out: Optional[torch.Ten
         n_out = mods[-1].out_features
         # the whole MLP as one f32-MFMA kernel (csrc/mlp.hip)
         return mlp3_forward(mods, x, _out_rows(out, x.numel() // x.shape[-1], n_out))
+    if mlp3.ENABLED and mlp3.WIDE_ENABLED and x.dtype == torch.float32 and mlp3.wide_layers(mods):
+        # 33..128 outputs (the centralised actor's joint action): the wide kernel (csrc/mlp_wide.hip),
+        # opt-in with MSC_WIDE_MLP=1
+        return mlp3.wide_forward(mods, x, _out_rows(out, x.numel() // x.shape[-1], mods[-1].out_features))
     i = 0
     while i < len(mods):
         m = mods[i]
@@ -575,13 +581,18 @@ def split_global_mlp(mlp: nn.Sequential, local_obs: torch.Tensor, agent: Optiona
 def fused_actor_sample(actor: nn.Sequential, x: torch.Tensor, sample) -> bool:
     """Run `actor` over x with msc_gaussian_sample fused into the MLP kernel's epilogue (sample =
     (log_std [P, K], logstd_floor, eps, actions, logp, clipped)); False (nothing launched) when the
-    fused kernel does not apply, e.g. more than 8 outputs or a non-ReLU MLP."""
+    fused kernel does not apply, e.g. 9..32 or more than 128 outputs, or a non-ReLU MLP. 33..128 outputs
+    (the centralised actor): the wide kernel's epilogue (mlp.wide_forward) with MSC_WIDE_MLP=1."""
     mods = list(actor)
-    if not (_FUSED and mlp3.ENABLED and x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled()
-            and mlp3.sample_fusable(mods)):
+    if not (_FUSED and mlp3.ENABLED and x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled()):
         return False
-    mlp3_forward(mods, x, None, sample=sample)
-    return True
+    if mlp3.sample_fusable(mods):
+        mlp3_forward(mods, x, None, sample=sample)
+        return True
+    if mlp3.WIDE_ENABLED and mlp3.wide_layers(mods):
+        mlp3.wide_forward(mods, x, None, sample=sample)
+        return True
+    return False
 
 
 def _vp(t: Optional[torch.Tensor]):
