@@ -126,13 +126,15 @@ def _reset_mask(reset: torch.Tensor, group: int, n: int) -> torch.Tensor:
 
 def torch_step(net, x: torch.Tensor, h: torch.Tensor, reset: Optional[torch.Tensor] = None, group: int = 1):
     """One step through the torch layers: x [..., in], h [..., layers, hidden] -> (y [..., out],
-    h' [..., layers, hidden]); rows whose group's reset flag is non-zero start from a zero state."""
+    h' [..., layers, hidden]); rows whose group's reset flag is non-zero start from a zero state
+    (selected, not multiplied: whatever their old state holds is not read, as in the kernel)."""
     g = net["gru"]
     lead = x.shape[:-1]
     xf = x.reshape(-1, x.shape[-1])
     hf = h.reshape(-1, g.num_layers, g.hidden_size)
-    if reset is not None:
-        hf = hf * _reset_mask(reset, group, hf.shape[0]).to(hf.dtype)[:, None, None]
+    if reset is not None:  # a select, as the kernel's: a reset row never reads its old state (NaN / Inf included)
+        zero = torch.zeros((), dtype=hf.dtype, device=hf.device)
+        hf = torch.where(_reset_mask(reset, group, hf.shape[0])[:, None, None], hf, zero)
     o, hn = g(xf.unsqueeze(1), hf.transpose(0, 1).contiguous())
     y = net["output_proj"](o[:, 0])
     return y.reshape(*lead, -1), hn.transpose(0, 1).reshape(*lead, g.num_layers, g.hidden_size)
