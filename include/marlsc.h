@@ -360,9 +360,17 @@ int msc_normal_keyed(float* out, int32_t n_steps, int64_t n_rows, int32_t row_le
  * state (device f64 [4 + 4 n_cols]): {n, buffer n, 0, 0, M[n_cols], S[n_cols], buffer M[n_cols],
  * buffer S[n_cols]}; the buffer collects the pushes since the caller last cleared it (RLlib's filter
  * buffer, merged across env runners by RunningStat.update). scratch: device f64
- * [msc_meanstd_scratch_doubles(n_rows, n_cols)] (only with update). Rows are pushed sequentially
- * within segments of ceil(n_rows / 64) rows and segment statistics combined by Chan's merge, so
- * results match a sequential update to rounding (f64). */
+ * [msc_meanstd_scratch_doubles(n_rows, n_cols)] (only with update; may be null without), with
+ * P = ceil(n_rows / G) segments of G = ceil(n_rows / min(n_rows, 64)) rows: 3 P n_cols segment
+ * statistics, 3 n_cols final statistics and the buffer count before the call, 3 (P + 1) n_cols + 1.
+ * The plan: each segment's rows are pushed sequentially from zero; a row of segment p is pushed into,
+ * and normalised with, the state merged with segments 0 .. p-1 in that order (RunningStat.update,
+ * m = (n1 m1 + n2 m2) / n, s = s1 + s2 + (delta^2 / n) n1 n2) and then the rows of p before it; the
+ * buffer absorbs segments 0 .. P-1. A segment without a pushed row is skipped, so a call that
+ * pushes nothing (an all-zero mask) leaves state as it is, bit for bit. Every operation is a float64
+ * + - * / or sqrt, none contracted: out and state equal the sequential float64 evaluation of this
+ * plan bit for bit (tests/meanstd_emulation.py), and a strictly sequential update to rounding. A
+ * call that fails an argument check writes nothing. */
 int64_t msc_meanstd_scratch_doubles(int64_t n_rows, int32_t n_cols);
 int msc_meanstd_filter(const float* obs, float* out, int64_t n_rows, int32_t n_cols, const uint8_t* mask,
                        int32_t update, double* state, double* scratch, double clip, double eps,

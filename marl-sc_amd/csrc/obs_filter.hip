@@ -17,7 +17,13 @@
 //                      rows pushed and normalised one by one (the reference's sequential update
 //                      inside a segment, Chan merges across segment boundaries);
 //   of_commit_kernel   thread c: the state after the last segment becomes the running state; the
-//                      buffer absorbs the segments.
+//                      buffer absorbs the segments. Every column's merge starts from the buffer count
+//                      before the call, and thread 0 writes the new count into state[1]: the threads
+//                      take the old count from the copy of_apply_kernel left in the scratch, never from
+//                      state[1], whose write nothing orders after the other waves' and blocks' reads.
+// A segment without a push (every row masked: the collector's apply(final_obs, mask = trunc) on a
+// step that truncates nothing) is skipped, not merged: rs_merge with an empty b computes
+// (n1 * m1 + 0) / n1, which is not m1 in every case, so a call that pushes nothing would move M.
 // Lanes are columns (rows are contiguous [E][C] f32), so every row read is coalesced. HBM traffic
 // per call: the obs read twice and written once (12 B per element); the rest is per column.
 #include <hip/hip_runtime.h>
@@ -59,7 +65,8 @@ __device__ __forceinline__ float rs_normalize(double x, double n, double m, doub
   return (float)y;
 }
 
-// state: {run_n, buf_n, 0, 0, run_M[C], run_S[C], buf_M[C], buf_S[C]}; seg: [P][C][3]
+// state: {run_n, buf_n, 0, 0, run_M[C], run_S[C], buf_M[C], buf_S[C]}
+// scratch: seg [P][C][3], fin [C][3], then the buffer count before the call [1]
 __global__ __launch_bounds__(OF_BS) void of_segment_kernel(const float* __restrict__ x, int64_t E, int32_t C,
                                                          const uint8_t* __restrict__ mask, int64_t G, int32_t P,
                                                          double* __restrict__ seg) {
@@ -89,7 +96,7 @@ __global__ __launch_bounds__(OF_BS) void of_apply_kernel(const float* __restrict
   if (update) {
     for (int q = 0; q < p; q++) {
       const double* g = seg + ((int64_t)q * C + c) * 3;
-      rs_merge(n, m, s, g[0], g[1], g[2]);
+      if (g[0] != 0.0) rs_merge(n, m, s, g[0], g[1], g[2]);
     }
   }
   for (int64_t e = e0; e < e1; e++) {
@@ -101,6 +108,7 @@ __global__ __launch_bounds__(OF_BS) void of_apply_kernel(const float* __restrict
     fin[(int64_t)c * 3 + 0] = n;
     fin[(int64_t)c * 3 + 1] = m;
     fin[(int64_t)c * 3 + 2] = s;
+    if (c == 0) fin[(int64_t)C * 3] = state[1];  // the buffer count of_commit_kernel's merges start from
   }
 }
 
@@ -108,10 +116,10 @@ __global__ __launch_bounds__(OF_BS) void of_commit_kernel(int32_t C, int32_t P, 
                                                         const double* __restrict__ fin, double* __restrict__ state) {
   const int c = (int)(blockIdx.x * OF_BS + threadIdx.x);
   if (c >= C) return;
-  double bn = state[1], bm = state[4 + 2 * C + c], bs = state[4 + 3 * C + c];
+  double bn = fin[(int64_t)C * 3], bm = state[4 + 2 * C + c], bs = state[4 + 3 * C + c];
   for (int q = 0; q < P; q++) {
     const double* g = seg + ((int64_t)q * C + c) * 3;
-    rs_merge(bn, bm, bs, g[0], g[1], g[2]);
+    if (g[0] != 0.0) rs_merge(bn, bm, bs, g[0], g[1], g[2]);
   }
   state[4 + c] = fin[(int64_t)c * 3 + 1];
   state[4 + C + c] = fin[(int64_t)c * 3 + 2];
@@ -132,7 +140,7 @@ int64_t meanstd_scratch_doubles(int64_t E, int32_t C) {
   int64_t G;
   int32_t P;
   meanstd_plan(E, &G, &P);
-  return (int64_t)P * C * 3 + (int64_t)C * 3;
+  return (int64_t)P * C * 3 + (int64_t)C * 3 + 1;
 }
 
 hipError_t launch_meanstd_filter(const float* x, float* out, int64_t E, int32_t C, const uint8_t* mask, int32_t update,

@@ -48,8 +48,11 @@ def merge_stats(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     m1, s1, m2, s2 = a[1:1 + C_], a[1 + C_:], b[1:1 + C_], b[1 + C_:]
     delta = m1 - m2
     delta2 = delta * delta
-    m = (n1 * m1 + n2 * m2) / n
-    s = s1 + s2 + (delta2 / n) * n1 * n2
+    # the divisor as a tensor: torch divides a device tensor by a Python number as x * (1 / n), which is
+    # not the correctly rounded quotient of the reference's update (and of the same call on the CPU)
+    nt = a[0] + b[0]
+    m = (n1 * m1 + n2 * m2) / nt
+    s = s1 + s2 + (delta2 / nt) * n1 * n2
     out = torch.empty_like(a)
     out[0] = n
     out[1:1 + C_] = m

@@ -99,3 +99,66 @@ def synchronize(driver: RunningStat, runner_filters):
         f.rs = driver.copy()
         f.buffer = RunningStat(driver.M.shape)
     return driver
+
+
+# ---- the high-precision reference ("truth") of the device filter's tests --------------------------------
+# The same model in np.longdouble (x87 extended: 64-bit mantissa, 11 bits more than the float64 the
+# kernels and the restatement above compute in), every column at once. A float64 evaluation's error
+# against it is that evaluation's own rounding; the Welford state is itself pinned to a two-pass mean
+# and centred sum of squares in the same format (tests/test_meanstd_exact_host.py).
+
+LD = np.longdouble
+assert np.finfo(LD).nmant >= 63, "the long double reference needs a 64-bit mantissa (x87 extended)"
+
+
+class LongdoubleStat:
+    """RunningStat over the columns of a row, in long double; n is an exact Python int."""
+
+    def __init__(self, n_cols, n=0, M=None, S=None):
+        self.n = int(n)
+        self.M = np.zeros(n_cols, LD) if M is None else np.asarray(M, LD).copy()
+        self.S = np.zeros(n_cols, LD) if S is None else np.asarray(S, LD).copy()
+
+    def push(self, x):
+        self.n += 1
+        if self.n == 1:
+            self.M[...] = x
+        else:
+            delta = x - self.M
+            self.M += delta / LD(self.n)
+            self.S += delta * delta * LD(self.n - 1) / LD(self.n)
+
+    @property
+    def var(self):
+        return self.S / LD(self.n - 1) if self.n > 1 else self.M * self.M
+
+
+class LongdoubleFilter:
+    """Push when not masked, then normalise with the statistics that include the row: running
+    statistics + buffer, like MeanStdFilter, but returning the unrounded long double outputs."""
+
+    def __init__(self, n_cols, clip=CLIP, eps=SMALL_NUMBER):
+        self.rs, self.buffer = LongdoubleStat(n_cols), LongdoubleStat(n_cols)
+        self.clip, self.eps = LD(clip), LD(eps)
+
+    def rows(self, x, mask=None, update=True):
+        """x [E, C] (float32 observations) -> long double [E, C]."""
+        x = np.asarray(x).astype(LD)
+        out = np.empty(x.shape, LD)
+        with np.errstate(all="ignore"):
+            for e in range(x.shape[0]):
+                if update and (mask is None or mask[e]):
+                    self.rs.push(x[e])
+                    self.buffer.push(x[e])
+                y = (x[e] - self.rs.M) / (np.sqrt(self.rs.var) + self.eps)
+                out[e] = np.clip(y, -self.clip, self.clip) if self.clip > 0 else y
+        return out
+
+
+def two_pass(rows):
+    """(n, mean, centred sum of squares) of rows [n, C] in long double, the textbook two passes."""
+    x = np.asarray(rows).astype(LD)
+    n = x.shape[0]
+    mean = x.sum(0) / LD(n)
+    d = x - mean
+    return n, mean, (d * d).sum(0)

@@ -2,7 +2,9 @@
 src/algorithms/mappo.py:170-171): the numpy restatement (oracle/meanstd_ref.py) pinned against
 numpy's own statistics, the host-side merge / synchronisation of marlsc/obs_filter.py against it,
 and the world_size-2 synchronisation over gloo. RLlib itself is not installed: parity with RLlib is
-unpinned; the device kernel is checked against the oracle in tests/test_gpu_rollout.py."""
+unpinned; the device kernels are pinned bit for bit to an emulation of their plan in
+tests/test_gpu_meanstd_exact.py (the emulation to a long double reference and its mutants in
+tests/test_meanstd_exact_host.py), and to the sequential oracle at 1e-5 in tests/test_gpu_rollout.py."""
 import os
 import socket
 import sys
