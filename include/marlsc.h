@@ -188,7 +188,7 @@ int msc_env_kernel_choice(const msc_env* env, int32_t* out, int32_t n);
  * (default: beside the pipelined demand kernel) or 4 (no register spills; the rollout collector's
  * choice, with policy kernels between steps). MSC_OPT_ALLOC_PRIO_SPLIT: the share, in 16ths of its
  * busiest env's orders, that each one-env-per-lane allocation wave runs above the pipelined demand
- * kernel's parser (s_setprio 3) before it drops below it (1 .. 16; default 12; 16: the whole kernel,
+ * kernel's parser (s_setprio 3) before it drops below it (1 .. 16; default 14; 16: the whole kernel,
  * the rollout collector's choice). Returns 0, or < 0 for an unknown key / value. */
 #define MSC_OPT_STEP_C_FORM 1
 #define MSC_OPT_ALLOC_PRIO_SPLIT 2
@@ -567,6 +567,15 @@ int msc_gru_step(const float* x, int64_t n_rows, int32_t in_dim, int32_t hidden,
  * msc_env_read_state's rng); draws -> out_host [n], the final state -> state_out_host (may be NULL). */
 int msc_poisson_draws(const uint64_t* state_host, const double* lam_host, int64_t n_lam, int64_t n,
                       int64_t* out_host, uint64_t* state_out_host);
+
+/* Utility: the demand generators' draw on the device (synchronous; exposed for known-answer tests).
+ * One 64-lane block: lane l starts from the 128-bit PCG64 state state_host[2l], state_host[2l + 1]
+ * ({high, low} halves) and n times writes numpy's random() of its state (the double's bit pattern,
+ * out_host[l * n + i]) and advances the state to state * M^stride + inc (mod 2^128), M the PCG64
+ * multiplier and inc the lane's stride increment inc_host[2l], inc_host[2l + 1] (any value);
+ * stride is 1, 2, 3, 5 or 7. The final states -> state_out_host [64][2]. */
+int msc_gen_draws(const uint64_t* state_host, const uint64_t* inc_host, int32_t stride, int64_t n, uint64_t* out_host,
+                  uint64_t* state_out_host);
 
 /* Utility: SeedSequence(words).generate_state(1, uint32)[0] (numpy-compatible), on the host. */
 uint32_t msc_seedseq_u32(const uint32_t* words, int32_t n_words);

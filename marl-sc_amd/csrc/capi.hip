@@ -516,9 +516,10 @@ int msc_env_create(const msc_env_desc* d, int device, int64_t n_envs, uint32_t b
     // alloc_lane's waves run above the parser of the next step's demand kernel for the first 12/16
     // of their orders, then below it: the pipelined C3 step is demand-bound with the allocation at
     // full priority (0.755 ms demand beside 0.64 ms of step kernels) and chain-bound below it (0.61
-    // beside 0.86); 12/16 balances them (341 -> 349 M agent-steps/s, profiles/r06/ab_alloc_prio.txt)
-    c.al_psplit = 12;
-    if (const char* ps = getenv("MSC_AL_PRIO_SPLIT")) c.al_psplit = atoi(ps) >= 1 && atoi(ps) <= 16 ? atoi(ps) : 12;
+    // beside 0.86); 12/16 balanced them (341 -> 349 M agent-steps/s, profiles/r06/ab_alloc_prio.txt), and
+    // 14/16 does with the shorter generator draw (361 -> 368 M, profiles/gen_draw/ab_alloc_prio.txt)
+    c.al_psplit = 14;
+    if (const char* ps = getenv("MSC_AL_PRIO_SPLIT")) c.al_psplit = atoi(ps) >= 1 && atoi(ps) <= 16 ? atoi(ps) : 14;
     if (const char* st = getenv("MSC_SC_TAB")) c.sc_tab = atoi(st) != 0 ? 1 : 0;
     c.sb_gw = 0;
     if (const char* g = getenv("MSC_SB_GW")) {
@@ -1391,6 +1392,32 @@ int msc_poisson_draws(const uint64_t* state_host, const double* lam_host, int64_
       (n > 0 && hipMemcpy(out_host, m + b_st + b_pc + b_el, sizeof(int64_t) * n, hipMemcpyDeviceToHost) != hipSuccess) ||
       (state_out_host && hipMemcpy(state_out_host, m, b_st, hipMemcpyDeviceToHost) != hipSuccess))
     rc = set_err(-2, "poisson draws: %s", hipGetErrorString(hipGetLastError()));
+  (void)hipFree(mem);
+  return rc;
+}
+
+int msc_gen_draws(const uint64_t* state_host, const uint64_t* inc_host, int32_t stride, int64_t n, uint64_t* out_host,
+                  uint64_t* state_out_host) {
+  if (!state_host || !inc_host || !out_host || !state_out_host) return set_err(-1, "null argument");
+  if (stride != 1 && stride != 2 && stride != 3 && stride != 5 && stride != 7)
+    return set_err(-1, "stride %d: must be 1, 2, 3, 5 or 7", stride);
+  if (n < 0 || n > (1 << 20)) return set_err(-1, "bad draw count %lld", (long long)n);
+  void* mem = nullptr;
+  const size_t b_st = 2 * 64 * sizeof(uint64_t), b_out = sizeof(uint64_t) * 64 * (size_t)(n > 0 ? n : 1);
+  if (hipMalloc(&mem, 3 * b_st + b_out) != hipSuccess) {
+    (void)hipGetLastError();
+    return set_err(-2, "hipMalloc failed");
+  }
+  char* m = (char*)mem;  // state [64][2], increment [64][2], final state [64][2], draws [64][n]
+  int rc = 0;
+  if (hipMemcpy(m, state_host, b_st, hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(m + b_st, inc_host, b_st, hipMemcpyHostToDevice) != hipSuccess ||
+      launch_gen_draws(stride, (const uint64_t*)m, (const uint64_t*)(m + b_st), n, (uint64_t*)(m + 3 * b_st),
+                       (uint64_t*)(m + 2 * b_st), 0) != hipSuccess ||
+      hipDeviceSynchronize() != hipSuccess ||
+      (n > 0 && hipMemcpy(out_host, m + 3 * b_st, sizeof(uint64_t) * 64 * (size_t)n, hipMemcpyDeviceToHost) != hipSuccess) ||
+      hipMemcpy(state_out_host, m + 2 * b_st, b_st, hipMemcpyDeviceToHost) != hipSuccess)
+    rc = set_err(-2, "generator draws: %s", hipGetErrorString(hipGetLastError()));
   (void)hipFree(mem);
   return rc;
 }

@@ -95,17 +95,14 @@ __global__ __launch_bounds__(BS * (1 + G)) __attribute__((amdgpu_waves_per_eu(MS
     uint64_t mh = PCG_MUL_HI, ml = PCG_MUL_LO, ch = ih, cl = il;
     if constexpr (G > 1) pcg_jump_coeffs(G, ih, il, mh, ml, ch, cl);
     int pg = g;
+    GenLane gl = gen_lane(th, tl, ch, cl);  // (the draw: gen_uniform / gen_advance, demand_common.hpp)
     auto gen_to = [&](int target) {
       while (pg < target) {
-        // numpy random(): (x >> 11) 2^-53 of the XSL-RR output x, as the top 32 bits 2^-32 plus the
-        // next 21 bits 2^-53 (one exact fma, pcg_output_double)
-        const uint64_t x = pcg_output(th, tl);
-        const double hi = (double)(uint32_t)vsettle((int)(uint32_t)(x >> 32));
-        const double u = fma(hi, 0x1p-32, (double)((uint32_t)x >> 11) * 0x1p-53);
+        const double u = gen_uniform(gl);
         const int sl = pg & (UCAP - 1);
         myring[sl * BS] = u;
         myring[(sl < UD - 1 ? sl + UCAP : USLOTS - 1) * BS] = u;  // mirror (or the dummy row)
-        lcg128(th, tl, mh, ml, ch, cl);
+        gen_advance<G>(gl);
         pg += G;
       }
     };
@@ -320,6 +317,38 @@ hipError_t launch_demand_v3(const EnvConst& c, const DevEnv* d, hipStream_t st, 
     case 6: launch_v3_k<6>(c, d, st, ea); break;
     case 7: launch_v3_k<7>(c, d, st, ea); break;
     case 8: launch_v3_k<8>(c, d, st, ea); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+// The generator waves' draw on given states (msc_gen_draws, known-answer tests): lane l of one
+// 64-lane block starts from state[l] with the stride increment inc[l] ({high, low} 64-bit halves),
+// writes n times the uniform of its state (as its bit pattern, out[l * n + i]) and advances by the
+// stride G, and leaves its final state in state_out[l].
+template <int G>
+__global__ __launch_bounds__(BS) void gen_draws_kernel(const uint64_t* __restrict__ state, const uint64_t* __restrict__ inc,
+                                                       int64_t n, uint64_t* __restrict__ out,
+                                                       uint64_t* __restrict__ state_out) {
+  if (blockIdx.x != 0) return;
+  const int lane = (int)threadIdx.x;
+  GenLane gl = gen_lane(state[2 * lane], state[2 * lane + 1], inc[2 * lane], inc[2 * lane + 1]);
+  for (int64_t i = 0; i < n; i++) {
+    out[(int64_t)lane * n + i] = (uint64_t)__double_as_longlong(gen_uniform(gl));
+    gen_advance<G>(gl);
+  }
+  state_out[2 * lane] = gen_state_hi(gl);
+  state_out[2 * lane + 1] = gen_state_lo(gl);
+}
+
+hipError_t launch_gen_draws(int G, const uint64_t* state, const uint64_t* inc, int64_t n, uint64_t* out,
+                            uint64_t* state_out, hipStream_t st) {
+  switch (G) {
+    case 1: hipLaunchKernelGGL(gen_draws_kernel<1>, dim3(1), dim3(BS), 0, st, state, inc, n, out, state_out); break;
+    case 2: hipLaunchKernelGGL(gen_draws_kernel<2>, dim3(1), dim3(BS), 0, st, state, inc, n, out, state_out); break;
+    case 3: hipLaunchKernelGGL(gen_draws_kernel<3>, dim3(1), dim3(BS), 0, st, state, inc, n, out, state_out); break;
+    case 5: hipLaunchKernelGGL(gen_draws_kernel<5>, dim3(1), dim3(BS), 0, st, state, inc, n, out, state_out); break;
+    case 7: hipLaunchKernelGGL(gen_draws_kernel<7>, dim3(1), dim3(BS), 0, st, state, inc, n, out, state_out); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();

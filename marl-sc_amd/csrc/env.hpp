@@ -231,6 +231,8 @@ hipError_t launch_demand_v2(const EnvConst& c, const DevEnv* d, hipStream_t st, 
 bool demand_v3_supported(const EnvConst& c);
 hipError_t launch_demand_v3(const EnvConst& c, const DevEnv* d, hipStream_t st, const EaLaunch* ea);
 hipError_t launch_demand_alt(const EnvConst& c, const DevEnv* d, hipStream_t st, const EaLaunch* ea);
+hipError_t launch_gen_draws(int G, const uint64_t* state, const uint64_t* inc, int64_t n, uint64_t* out,
+                            uint64_t* state_out, hipStream_t st);
 int order_record_vec4(int K);
 // gae.hip
 hipError_t launch_gae(const float* r, const float* v, const float* nv, const uint8_t* term, const uint8_t* trunc,

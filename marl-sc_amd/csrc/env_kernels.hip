@@ -434,13 +434,14 @@ __global__ __launch_bounds__(BS * (1 + G)) __attribute__((amdgpu_waves_per_eu(MS
     uint64_t mh = PCG_MUL_HI, ml = PCG_MUL_LO, ch = ih, cl = il;
     if constexpr (G > 1) pcg_jump_coeffs(G, ih, il, mh, ml, ch, cl);
     int pg = g;
+    GenLane gl = gen_lane(th, tl, ch, cl);  // (the draw: gen_uniform / gen_advance, demand_common.hpp)
     auto gen_to = [&](int target) {
       while (pg < target) {
-        const double u = pcg_output_double(th, tl);
+        const double u = gen_uniform(gl);
         const int slot = pg & (UCAP - 1);
         myring[slot * BS] = u;
         myring[(slot < UD - 1 ? slot + UCAP : USLOTS - 1) * BS] = u;  // mirror (or the dummy row)
-        lcg128(th, tl, mh, ml, ch, cl);
+        gen_advance<G>(gl);
         pg += G;
       }
     };

@@ -113,6 +113,7 @@ def lib() -> C.CDLL:
     L.msc_env_destroy.argtypes = [vp]
     L.msc_env_destroy.restype = None
     L.msc_poisson_draws.argtypes = [vp, vp, C.c_int64, C.c_int64, vp, vp]
+    L.msc_gen_draws.argtypes = [vp, vp, C.c_int32, C.c_int64, vp, vp]
     L.msc_normal_keyed.argtypes = [vp, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_uint64, C.c_uint64, vp]
     L.msc_env_set_episode_ahead.argtypes = [vp, C.c_int32]
     L.msc_env_ea_memory.argtypes = [vp, P(C.c_int64), P(C.c_int64)]
@@ -195,5 +196,5 @@ EXPORTED_SYMBOLS = [
     "msc_mlp_musigma_layout", "msc_mlp3_relu_musigma", "msc_mlp2_relu_musigma",
     "msc_mlp_wide_supported", "msc_mlp3_relu_wide", "msc_mlp2_relu_wide", "msc_reward_team_sum",
     "msc_gru_supported", "msc_gru_step",
-    "msc_normal_keyed", "msc_poisson_draws", "msc_meanstd_scratch_doubles", "msc_meanstd_filter", "msc_seedseq_u32", "msc_last_error", "msc_abi_version",
+    "msc_normal_keyed", "msc_poisson_draws", "msc_gen_draws", "msc_meanstd_scratch_doubles", "msc_meanstd_filter", "msc_seedseq_u32", "msc_last_error", "msc_abi_version",
 ]
