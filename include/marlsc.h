@@ -560,6 +560,46 @@ int msc_gru_step(const float* x, int64_t n_rows, int32_t in_dim, int32_t hidden,
                  const float* h_in, const msc_gru_weights* w, int32_t act_pre, int32_t act_out, const uint8_t* reset,
                  int32_t reset_group, float* y, float* h_out, msc_stream_t stream);
 
+/* Heuristic baseline policies on the device state of a handle: replaces the action functions of the
+ * reference's src/experiments/run_baselines.py, which read the env object between two steps --
+ *   MSC_POLICY_BASE_STOCK <- make_bs_newsvendor_action_fn / make_bs_optimized_action_fn  run_baselines.py:133-207, :296-337
+ *   MSC_POLICY_ADAPTIVE   <- make_adaptive_bs_action_fn                                   run_baselines.py:209-294
+ *   MSC_POLICY_RANDOM     <- make_random_action_fn                                        run_baselines.py:73-94
+ * (the constant-order policy, :96-131, is a fixed action tensor of the caller). msc_policy_act writes
+ * the actions [E][W][K] of every env in one launch on `stream`, from the env's on-hand inventory, its
+ * pending orders (env._compute_pending_matrix), last step's home demand (env._incoming_demand_home)
+ * and timestep as they stand between two msc_env_step calls (after an in-step auto-reset: the new
+ * episode's). With q(x) = min(max(x, 0), maxq[k]) and act(x) = (float)(2 q(x) / maxq[k] - 1), all
+ * float64 with one rounding to float32 (maxq = the `direct` action space's max_order_quantities):
+ *   base-stock: act(S[cand[e]][w, k] - inventory - pending);
+ *   adaptive:   at timestep 0 the env's demand window is cleared and every action is -1; otherwise
+ *               last step's home demand is appended and, over the window's last n = min(count,
+ *               H[cand[e]]) entries, oldest first: mean = float32 sequential sum / (float)n; var = mean
+ *               when n == 1, else the float32 sequential sum of (x - mean) * (x - mean) / (float)n
+ *               (numpy's axis-0 mean / var of a float32 stack); S = L mean + z[cand[e]] sqrt(L var) in
+ *               float64 with L the expected lead time; act(S - inventory - pending);
+ *   random:     W * K draws of numpy's Generator.random() in (agent, SKU) order from the env's own
+ *               PCG64 state, (float)(-1.0 + 2.0 u) (Generator.uniform(-1, 1) cast to float32).
+ * Every env carries a candidate index cand[e] < n_candidates into the tables S [n_candidates][W*K]
+ * f64, z [n_candidates] f64, H [n_candidates] i32, so one handle sweeps many parameter sets at once.
+ * msc_policy_create (synchronous) takes HOST arrays: S_host (base-stock), z_host and H_host (adaptive;
+ * 1 <= H <= h_max, h_max <= 0: the largest H given), cand_host [E] (NULL: all 0), rng_state_host
+ * [E][4] u64 {state_hi, state_lo, inc_hi, inc_lo} (random); arrays a kind does not use may be NULL.
+ * The env's action space must be `direct` (the reference's baselines assume it too). The demand
+ * window [h_max][W*K][E], its count and the RNG states belong to the policy, not to the env: they are
+ * not part of msc_env_save_state. msc_policy_set_tables (synchronous) replaces S / z / H / cand (NULL:
+ * kept) for the same n_candidates without reallocating. An argument error returns < 0 with a message
+ * and launches nothing. */
+typedef struct msc_policy msc_policy;
+enum msc_policy_kind { MSC_POLICY_BASE_STOCK = 0, MSC_POLICY_ADAPTIVE = 1, MSC_POLICY_RANDOM = 2 };
+int msc_policy_create(const msc_env* env, int32_t kind, int32_t n_candidates, int32_t h_max, const double* S_host,
+                      const double* z_host, const int32_t* H_host, const int32_t* cand_host,
+                      const uint64_t* rng_state_host, msc_policy** out);
+int msc_policy_act(msc_policy* policy, const msc_env* env, float* actions, msc_stream_t stream);
+int msc_policy_set_tables(msc_policy* policy, int32_t n_candidates, const double* S_host, const double* z_host,
+                          const int32_t* H_host, const int32_t* cand_host);
+void msc_policy_destroy(msc_policy* policy);
+
 /* Utility: numpy's Generator.poisson on the device (synchronous; the env's own sampler, exposed for
  * known-answer tests): n draws with the rates lam_host[i % n_lam] (random_poisson: multiplication
  * method below 10, PTRS at or above, numpy/random/src/distributions/distributions.c) from the PCG64

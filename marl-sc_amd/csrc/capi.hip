@@ -1724,3 +1724,141 @@ int msc_env_set_episode_counters(msc_env* env, const int32_t* counters_host) {
 }
 
 }  // extern "C"
+
+// ---- baseline policies (policy.hip) ---------------------------------------------------------
+struct msc_policy {
+  PolicyDev p = {};
+  int device = 0;
+  int64_t E = 0;
+  int32_t WK = 0;
+  void* mem = nullptr;  // one allocation: tables, candidate map, then the kind's own state
+};
+
+// validate the host tables of a policy of `kind` for n_cand candidates and E envs (h_max > 0: the bound on H)
+static int policy_check_tables(int kind, int n_cand, int64_t E, int WK, int h_max, const double* S, const double* z,
+                               const int32_t* H, const int32_t* cand) {
+  if (kind == MSC_POLICY_BASE_STOCK && S)
+    for (int64_t i = 0; i < (int64_t)n_cand * WK; i++)
+      if (!(S[i] == S[i]) || fabs(S[i]) > 1e300) return set_err(-1, "base-stock level %lld is not finite", (long long)i);
+  if (kind == MSC_POLICY_ADAPTIVE) {
+    for (int i = 0; z && i < n_cand; i++)
+      if (!(z[i] == z[i]) || fabs(z[i]) > 1e300) return set_err(-1, "safety factor z[%d] is not finite", i);
+    for (int i = 0; H && i < n_cand; i++) {
+      if (H[i] < 1) return set_err(-1, "window H[%d] = %d must be >= 1", i, H[i]);
+      if (h_max > 0 && H[i] > h_max) return set_err(-1, "window H[%d] = %d exceeds h_max %d", i, H[i], h_max);
+    }
+  }
+  for (int64_t e = 0; cand && e < E; e++)
+    if (cand[e] < 0 || cand[e] >= n_cand)
+      return set_err(-1, "candidate index %d of env %lld is outside [0, %d)", cand[e], (long long)e, n_cand);
+  return 0;
+}
+
+static size_t up256(size_t n) { return (n + 255) & ~(size_t)255; }
+
+extern "C" {
+
+int msc_policy_create(const msc_env* env, int32_t kind, int32_t n_cand, int32_t h_max, const double* S_host,
+                      const double* z_host, const int32_t* H_host, const int32_t* cand_host,
+                      const uint64_t* rng_state_host, msc_policy** out) {
+  if (!env || !out) return set_err(-1, "null argument");
+  if (kind != MSC_POLICY_BASE_STOCK && kind != MSC_POLICY_ADAPTIVE && kind != MSC_POLICY_RANDOM)
+    return set_err(-1, "unknown policy kind %d", kind);
+  if (env->c.action_type != MSC_ACTION_DIRECT)
+    return set_err(-1, "baseline policies need the `direct` action space (action_type %d)", env->c.action_type);
+  if (n_cand < 1) return set_err(-1, "n_candidates %d must be >= 1", n_cand);
+  const int64_t E = env->c.E;
+  const int WK = env->c.W * env->c.K;
+  if (kind == MSC_POLICY_BASE_STOCK && !S_host) return set_err(-1, "base-stock policy needs S_host");
+  if (kind == MSC_POLICY_ADAPTIVE && (!z_host || !H_host)) return set_err(-1, "adaptive policy needs z_host and H_host");
+  if (kind == MSC_POLICY_RANDOM && !rng_state_host) return set_err(-1, "random policy needs rng_state_host");
+  if (const int rc = policy_check_tables(kind, n_cand, E, WK, h_max > 0 ? h_max : 0, S_host, z_host, H_host, cand_host))
+    return rc;
+  int hm = 0;
+  if (kind == MSC_POLICY_ADAPTIVE) {
+    hm = h_max;
+    if (hm <= 0)
+      for (int i = 0; i < n_cand; i++) hm = H_host[i] > hm ? H_host[i] : hm;
+    if ((double)hm * WK * (double)E * 4.0 > 64e9) return set_err(-1, "demand window of h_max %d is too large", hm);
+  }
+  const size_t oS = 0, oz = oS + up256(sizeof(double) * (size_t)n_cand * WK), oH = oz + up256(sizeof(double) * n_cand),
+               oc = oH + up256(sizeof(int32_t) * n_cand), ocnt = oc + up256(sizeof(int32_t) * E),
+               orng = ocnt + up256(sizeof(int32_t) * E), ohist = orng + up256(sizeof(uint64_t) * 4 * E),
+               total = ohist + up256(sizeof(int32_t) * (size_t)hm * WK * E);
+  HIP_TRY(hipSetDevice(env->device));
+  void* mem = nullptr;
+  HIP_TRY(hipMalloc(&mem, total));
+  msc_policy* pol = new msc_policy();
+  pol->mem = mem;
+  pol->device = env->device;
+  pol->E = E;
+  pol->WK = WK;
+  char* b = (char*)mem;
+  pol->p.kind = kind;
+  pol->p.n_cand = n_cand;
+  pol->p.h_max = hm;
+  pol->p.S = (double*)(b + oS);
+  pol->p.z = (double*)(b + oz);
+  pol->p.H = (int32_t*)(b + oH);
+  pol->p.cand = (int32_t*)(b + oc);
+  pol->p.count = (int32_t*)(b + ocnt);
+  pol->p.rng = (uint64_t*)(b + orng);
+  pol->p.hist = (int32_t*)(b + ohist);
+  hipError_t err = hipMemset(mem, 0, total);
+  if (err == hipSuccess && kind == MSC_POLICY_RANDOM) {
+    std::vector<uint64_t> tr((size_t)4 * E);  // [E][4] -> [4][E]
+    for (int64_t e = 0; e < E; e++)
+      for (int j = 0; j < 4; j++) tr[(size_t)j * E + e] = rng_state_host[e * 4 + j];
+    err = hipMemcpy(pol->p.rng, tr.data(), sizeof(uint64_t) * 4 * E, hipMemcpyHostToDevice);
+  }
+  if (err != hipSuccess) {
+    (void)hipFree(mem);
+    delete pol;
+    return set_err(-2, "policy state upload: %s", hipGetErrorString(err));
+  }
+  if (const int rc = msc_policy_set_tables(pol, n_cand, S_host, z_host, H_host, cand_host)) {
+    msc_policy_destroy(pol);
+    return rc;
+  }
+  *out = pol;
+  return 0;
+}
+
+int msc_policy_set_tables(msc_policy* pol, int32_t n_cand, const double* S_host, const double* z_host,
+                          const int32_t* H_host, const int32_t* cand_host) {
+  if (!pol) return set_err(-1, "null policy");
+  if (n_cand != pol->p.n_cand)
+    return set_err(-1, "n_candidates %d differs from the %d the policy was created with", n_cand, pol->p.n_cand);
+  const int kind = pol->p.kind;
+  if (const int rc = policy_check_tables(kind, n_cand, pol->E, pol->WK, pol->p.h_max, S_host, z_host, H_host, cand_host))
+    return rc;
+  HIP_TRY(hipSetDevice(pol->device));
+  HIP_TRY(hipDeviceSynchronize());  // launches that read the old tables have finished
+  if (kind == MSC_POLICY_BASE_STOCK && S_host)
+    HIP_TRY(hipMemcpy((void*)pol->p.S, S_host, sizeof(double) * (size_t)n_cand * pol->WK, hipMemcpyHostToDevice));
+  if (kind == MSC_POLICY_ADAPTIVE && z_host)
+    HIP_TRY(hipMemcpy((void*)pol->p.z, z_host, sizeof(double) * n_cand, hipMemcpyHostToDevice));
+  if (kind == MSC_POLICY_ADAPTIVE && H_host)
+    HIP_TRY(hipMemcpy((void*)pol->p.H, H_host, sizeof(int32_t) * n_cand, hipMemcpyHostToDevice));
+  if (cand_host) HIP_TRY(hipMemcpy((void*)pol->p.cand, cand_host, sizeof(int32_t) * pol->E, hipMemcpyHostToDevice));
+  return 0;
+}
+
+int msc_policy_act(msc_policy* pol, const msc_env* env, float* actions, msc_stream_t stream) {
+  if (!pol || !env || !actions) return set_err(-1, "null argument");
+  if (env->c.E != pol->E || env->c.W * env->c.K != pol->WK || env->device != pol->device)
+    return set_err(-1, "policy was created for another env shape or device");
+  if (env->c.action_type != MSC_ACTION_DIRECT) return set_err(-1, "baseline policies need the `direct` action space");
+  HIP_TRY(launch_policy_act(env->c, env->dev, pol->p, actions, (hipStream_t)stream));
+  return 0;
+}
+
+void msc_policy_destroy(msc_policy* pol) {
+  if (!pol) return;
+  (void)hipSetDevice(pol->device);
+  (void)hipDeviceSynchronize();
+  if (pol->mem) (void)hipFree(pol->mem);
+  delete pol;
+}
+
+}  // extern "C"

@@ -234,6 +234,18 @@ hipError_t launch_demand_alt(const EnvConst& c, const DevEnv* d, hipStream_t st,
 hipError_t launch_gen_draws(int G, const uint64_t* state, const uint64_t* inc, int64_t n, uint64_t* out,
                             uint64_t* state_out, hipStream_t st);
 int order_record_vec4(int K);
+// policy.hip: the baseline policies' action kernel (msc_policy_act). Device pointers; tables by candidate
+struct PolicyDev {
+  int32_t kind, n_cand, h_max;
+  const double* S;      // [n_cand][W*K] base-stock levels
+  const double* z;      // [n_cand]
+  const int32_t* H;     // [n_cand]
+  const int32_t* cand;  // [E] candidate of each env
+  int32_t* hist;        // [h_max][W*K][E] adaptive: home demand of the episode's steps, slot = step % h_max
+  int32_t* count;       // [E] adaptive: demands pushed this episode
+  uint64_t* rng;        // [4][E] random: PCG64 {s_hi, s_lo, i_hi, i_lo}
+};
+hipError_t launch_policy_act(const EnvConst& c, const DevEnv* d, const PolicyDev& p, float* actions, hipStream_t st);
 // gae.hip
 hipError_t launch_gae(const float* r, const float* v, const float* nv, const uint8_t* term, const uint8_t* trunc,
                       int64_t n, int32_t T, float gamma, float lam, float* adv, float* tgt, int32_t n_groups,

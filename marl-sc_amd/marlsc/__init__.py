@@ -15,7 +15,12 @@ __all__ = [
     "SeedManager", "default_train_seed", "EnvSpec", "make_synthetic_env_config",
     "VecInventoryEnv", "InventoryEnvironment", "CentralizedEnvWrapper", "VecCentralizedEnv",
     "CPPOConfig", "CPPOTrainer", "CentralizedRolloutEnv", "CentralizedActorCritic",
+    "RandomPolicy", "ConstantPolicy", "BaseStockPolicy", "AdaptiveBaseStockPolicy", "newsvendor_levels",
+    "rollout_episodes", "calibrate_demand", "validation_sweep", "evaluate_levels", "optimize_levels",
 ]
+
+_BASELINES = ("RandomPolicy", "ConstantPolicy", "BaseStockPolicy", "AdaptiveBaseStockPolicy", "newsvendor_levels",
+              "rollout_episodes", "calibrate_demand", "validation_sweep", "evaluate_levels", "optimize_levels")
 
 
 def __getattr__(name):  # torch-dependent modules load lazily
@@ -31,4 +36,7 @@ def __getattr__(name):  # torch-dependent modules load lazily
     if name in ("CPPOConfig", "CPPOTrainer", "CentralizedRolloutEnv", "CentralizedActorCritic"):
         from . import cppo
         return getattr(cppo, name)
+    if name in _BASELINES:
+        from . import baselines
+        return getattr(baselines, name)
     raise AttributeError(name)

@@ -22,6 +22,7 @@ LOST = {"closest": 0, "shipment": 1, "cost": 2}
 SCOPE = {"agent": 0, "team": 1}
 OBS_NORM = {"off": 0, "ratio": 1, "meanstd": 2}
 RESET_EVAL_RESTART = 1
+POLICY_BASE_STOCK, POLICY_ADAPTIVE, POLICY_RANDOM = 0, 1, 2  # include/marlsc.h msc_policy_kind
 
 # (feature key, bit) in _build_local_obs block order (multi_env.py:620-695)
 FEATURE_BITS = [
@@ -172,6 +173,11 @@ def lib() -> C.CDLL:
     L.msc_meanstd_scratch_doubles.argtypes = [C.c_int64, C.c_int32]
     L.msc_meanstd_scratch_doubles.restype = C.c_int64
     L.msc_meanstd_filter.argtypes = [vp, vp, C.c_int64, C.c_int32, vp, C.c_int32, vp, vp, C.c_double, C.c_double, vp]
+    L.msc_policy_create.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, P(vp)]
+    L.msc_policy_act.argtypes = [vp, vp, vp, vp]
+    L.msc_policy_set_tables.argtypes = [vp, C.c_int32, vp, vp, vp, vp]
+    L.msc_policy_destroy.argtypes = [vp]
+    L.msc_policy_destroy.restype = None
     L.msc_seedseq_u32.argtypes = [P(C.c_uint32), C.c_int32]
     L.msc_seedseq_u32.restype = C.c_uint32
     L.msc_last_error.restype = C.c_char_p
@@ -196,5 +202,6 @@ EXPORTED_SYMBOLS = [
     "msc_mlp_musigma_layout", "msc_mlp3_relu_musigma", "msc_mlp2_relu_musigma",
     "msc_mlp_wide_supported", "msc_mlp3_relu_wide", "msc_mlp2_relu_wide", "msc_reward_team_sum",
     "msc_gru_supported", "msc_gru_step",
+    "msc_policy_create", "msc_policy_act", "msc_policy_set_tables", "msc_policy_destroy",
     "msc_normal_keyed", "msc_poisson_draws", "msc_gen_draws", "msc_meanstd_scratch_doubles", "msc_meanstd_filter", "msc_seedseq_u32", "msc_last_error", "msc_abi_version",
 ]
