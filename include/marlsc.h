@@ -501,7 +501,25 @@ int msc_reward_team_sum(const double* rewards, int64_t n_envs, int32_t n_agents,
  * per-head register width / stride, or an error when there is no dual-head kernel: k outside 1..8,
  * unsupported hidden sizes (one hidden layer: up to 1024 units for k <= 4, 512 above), the MFMA
  * output layer forced (MSC_MLP_V3=0), or a [256, 256] A/B form without a head variant
- * (MSC_MLP_P8 = 4 / 2). */
+ * (MSC_MLP_P8 = 4 / 2).
+ * Exactness. The pre-activations o are sums of exact products accumulated in float32, as
+ * msc_mlp3_relu_forward's: with integer x, weights, biases and pre1 under its headroom condition
+ * they are the integer evaluation, and so are they, as num / 2^s, when rows of W_eff and b_eff are
+ * such integers scaled by powers of two. On an exact o:
+ *   MSC_ACT_NONE and MSC_ACT_RELU are exact; MSC_ACT_ELU (alpha = 1) returns o itself for o > 0;
+ *   tanh, ELU's negative branch, GELU and sigmoid stay within 4 max(e32, 1) units of the float64
+ *   value, one unit being 2^-24 |f(o)| (for GELU 2^-24 max(|f(o)|, |o| / 2): it is computed as
+ *   0.5 o (1 + erf(o / sqrt 2)), whose last factor carries an absolute error), and e32 the error of
+ *   a float32 evaluation of the same formula operation by operation (1.4 to 2.7 units). Measured:
+ *   at most 0.32 of that bound ("Mu/sigma head"). The sigmoid 1 / (1 + expf(-o)) is 0
+ *   for o < -88.7, where the true value is a float32 denormal: no relative bound is claimed there;
+ *   the clamp is exact: a log_std whose activation lies past a limit by more than the bound above is
+ *   that limit's float32 value, and mu is never clamped.
+ * Only columns < k are stored or sampled: whp's padded columns and what lies past bh[2k) and past
+ * eps[n_rows * k) are not read into any result, and nothing is written past n_rows rows of the four
+ * outputs (n_rows = 0 launches nothing). An activation code outside MSC_ACT_* is an error, not NONE.
+ * tests/test_gpu_musigma_exact.py holds every hidden-size branch, pass form and one-layer form to
+ * this for k = 1..8. */
 #define MSC_ACT_NONE 0
 #define MSC_ACT_RELU 1
 #define MSC_ACT_TANH 2

@@ -86,15 +86,16 @@ def int_case(L, hidden, KO, recipe, n, seed=0, pre1_group=0):
     return case
 
 
-def int_head_case(L, hidden, K, n, seed=0):
+def int_head_case(L, hidden, K, n, seed=0, pre1_group=0):
     """An integer mu / sigma-head actor: recipe-A hidden layers, a sparse integer backbone output
     Linear W_out [H, H] ({-1, 0, 1}, four non-zeros per row on average) and integer heads in [-2, 2],
     so that the fold W_eff = [W_mu; W_sigma] W_out, b_eff = [W_mu; W_sigma] b_out + [b_mu; b_sigma]
     is an exact integer matrix of small entries and the folded network keeps the headroom.
+    pre1_group > 0: int_case's integer pre1 (drawn after everything else: the weights do not change).
     Returns the case of the folded network (W[-1] = W_eff [2K, H]) plus the module weights under
     "out" (W_out, b_out), "mu" and "sigma" ((W, b) each)."""
     rng = np.random.default_rng([L, K, n, seed, 77] + list(hidden))
-    case = int_case(L, hidden, 2 * K, "A", n, seed)
+    case = int_case(L, hidden, 2 * K, "A", n, seed, pre1_group)
     H = hidden[-1]
     w_out = _sparse_signs(rng, (H, H), 4.0 / H)
     b_out = rng.integers(-3, 4, size=H)
