@@ -329,6 +329,61 @@ int msc_gae_grouped(const float* rewards, const float* values, const float* next
 int msc_adv_normalize_grouped(float* advantages, int64_t n, int32_t n_groups, const double* stats,
                               msc_stream_t stream);
 
+/* The PPO minibatch loss, its statistics and its gradients with respect to the network outputs in one
+ * launch: RLlib 2.52.1 PPOTorchLearner.compute_loss_for_module with the reference's hysteretic
+ * advantage weighting (src/algorithms/learners/hysteretic_learner.py:35-42: negative advantages
+ * scaled by hysteretic_beta). Output row i of n_rows uses batch row b = idx[i] (idx device int64
+ * [n_rows]; NULL: b = i), so the caller passes the whole batch's columns and the kernel gathers the
+ * minibatch. Repeated indices are legal. Every idx[i] must lie in [0, B), B the rows of the batch
+ * columns: that is the caller's contract, as with array indexing, and is not checked.
+ *   mean [n_rows][k], values [n_rows]; log_std [n_rows][k] (log_std_rows = 0: a mu/sigma head) or one
+ *   shared row [k] (log_std_rows = 1: the free parameter, already clamped at its floor by the caller);
+ *   actions [B][k], logp_old / advantages / value_targets [B], and with use_kl mean_old / log_std_old
+ *   [B][k] (NULL without). All float32 device buffers. Per row, with a the action:
+ *     logp = sum_k -(a - mean)^2 / (2 exp(log_std)^2) - log_std - log(2 pi) / 2
+ *     r    = exp(logp - logp_old),  A' = A if A >= 0 else hysteretic_beta A  (hysteretic_beta 1: off)
+ *     surr = min(A' r, A' clamp(r, 1 - clip_param, 1 + clip_param))
+ *     vfc  = clamp((values - value_targets)^2, 0, vf_clip_param),  ent = sum_k log_std + log(2 pi e) / 2
+ *     kl   = sum_k log_std - log_std_old + (exp(2 log_std_old) + (mean_old - mean)^2) / (2 exp(2 log_std)) - 1/2
+ *   total = mean_i(-surr + vf_loss_coeff vfc - entropy_coeff ent) + kl_coeff mean_i(kl)   (kl: use_kl only)
+ * Outputs: total (device f32[1]); stats (device f64[5]) = {total_loss, policy_loss = mean(-surr),
+ * vf_loss = mean(vfc), entropy = mean(ent), mean_kl = mean(kl)}, stored, or with accumulate_stats
+ * added to what the buffer holds (a learner sums over steps on the device and reads once);
+ * grad_mean [n_rows][k], grad_values [n_rows] and grad_log_std ([n_rows][k], or the row-summed [k] for
+ * the shared row) = d total / d (mean, values, log_std as given: a clamp of the free parameter stays
+ * with the caller). The gradients are torch autograd's, conventions at the kinks included:
+ * torch.minimum splits the gradient at a tie and torch.clamp passes it at its bounds, inclusive, so
+ *   - inside the clip range (A' r equals A' clamp(r)) the two halves add to the full A' r term, and a
+ *     ratio exactly at 1 -+ clip_param still gets it;
+ *   - (values - value_targets)^2 exactly equal to vf_clip_param still gets 2 (values - value_targets);
+ *   - a row with a clipped surrogate (and no KL term) or a zero advantage has grad_mean exactly 0, a
+ *     row with a clipped value error has grad_values exactly 0.
+ * The clip bounds are 1 -+ clip_param formed in float64 and rounded to float32, as torch forms them.
+ * Arithmetic: float32 per row, one rounding per operation, nothing contracted; the sums over rows
+ * (the statistics, the shared row's gradient) are float64 in a fixed order with no atomics, so equal
+ * calls give equal bits. workspace: msc_ppo_loss_workspace(n_rows, k) bytes of device memory
+ * (per-block partials; 8-byte aligned; -1 for a bad shape), which the call neither allocates nor
+ * keeps; it launches two kernels on `stream` and synchronises nothing.
+ * Errors (msc_last_error, nothing launched): n_rows <= 0, k outside [1, 128], a null desc or required
+ * pointer (idx may be null; mean_old / log_std_old only without use_kl). */
+typedef struct msc_ppo_loss_desc {
+  double clip_param;
+  double vf_clip_param;
+  double vf_loss_coeff;
+  double entropy_coeff;
+  double kl_coeff;
+  double hysteretic_beta;   /* in (0, 1]; 1 = off */
+  int32_t use_kl;
+  int32_t log_std_rows;     /* 1 = one shared row [k], 0 = per row [n_rows][k] */
+  int32_t accumulate_stats;
+} msc_ppo_loss_desc;
+int64_t msc_ppo_loss_workspace(int64_t n_rows, int32_t k);
+int msc_ppo_loss(const msc_ppo_loss_desc* desc, const float* mean, const float* log_std, const float* values,
+                 const int64_t* idx, const float* actions, const float* logp_old, const float* advantages,
+                 const float* value_targets, const float* mean_old, const float* log_std_old, int64_t n_rows,
+                 int32_t k, float* grad_mean, float* grad_log_std, float* grad_values, float* total, double* stats,
+                 void* workspace, msc_stream_t stream);
+
 /* Rollout action sampling (RLlib TorchDiagGaussian, rlmodules/base.py:480-557) over N rows of K:
  *   std = exp(max(log_std[n % log_std_rows][k], logstd_floor)) (one shared row, or one per agent
  *   with rows n = env * W + agent), actions = mean + std * eps (eps: standard normal draws),

@@ -1352,6 +1352,40 @@ int msc_gae(const float* rewards, const float* values, const float* next_values,
                          targets, 1, stats_out, stream);
 }
 
+int64_t msc_ppo_loss_workspace(int64_t n_rows, int32_t k) {
+  return n_rows >= 1 && k >= 1 && k <= 128 ? ppo_loss_workspace_bytes(n_rows, k) : -1;
+}
+
+int msc_ppo_loss(const msc_ppo_loss_desc* desc, const float* mean, const float* log_std, const float* values,
+                 const int64_t* idx, const float* actions, const float* logp_old, const float* advantages,
+                 const float* value_targets, const float* mean_old, const float* log_std_old, int64_t n_rows,
+                 int32_t k, float* grad_mean, float* grad_log_std, float* grad_values, float* total, double* stats,
+                 void* workspace, msc_stream_t stream) {
+  if (!desc) return set_err(-1, "msc_ppo_loss: null desc");
+  if (n_rows <= 0 || k < 1 || k > 128)
+    return set_err(-1, "msc_ppo_loss: bad shape (n_rows %lld must be >= 1, k %d in [1, 128])", (long long)n_rows, k);
+  if (!mean || !log_std || !values || !actions || !logp_old || !advantages || !value_targets || !grad_mean ||
+      !grad_log_std || !grad_values || !total || !stats || !workspace)
+    return set_err(-1, "msc_ppo_loss: null argument");
+  if (desc->use_kl && (!mean_old || !log_std_old))
+    return set_err(-1, "msc_ppo_loss: use_kl needs mean_old and log_std_old");
+  if (desc->log_std_rows != 0 && desc->log_std_rows != 1)
+    return set_err(-1, "msc_ppo_loss: log_std_rows %d must be 1 (shared row) or 0 (per row)", desc->log_std_rows);
+  PpoLossArgs a;
+  a.mean = mean, a.log_std = log_std, a.values = values, a.idx = idx;
+  a.actions = actions, a.logp_old = logp_old, a.advantages = advantages, a.value_targets = value_targets;
+  a.mean_old = mean_old, a.log_std_old = log_std_old;
+  a.grad_mean = grad_mean, a.grad_log_std = grad_log_std, a.grad_values = grad_values;
+  a.n = n_rows, a.K = k, a.use_kl = desc->use_kl ? 1 : 0, a.shared = desc->log_std_rows;
+  a.lo = (float)(1.0 - desc->clip_param), a.hi = (float)(1.0 + desc->clip_param);
+  a.vf_clip = (float)desc->vf_clip_param, a.c_v = (float)desc->vf_loss_coeff, a.c_e = (float)desc->entropy_coeff;
+  a.kl_coeff = desc->use_kl ? (float)desc->kl_coeff : 0.0f;
+  a.beta = (float)desc->hysteretic_beta;
+  a.inv_n = 1.0f / (float)n_rows;
+  HIP_TRY(launch_ppo_loss(a, desc->accumulate_stats ? 1 : 0, total, stats, workspace, (hipStream_t)stream));
+  return 0;
+}
+
 int msc_gaussian_sample(const float* mean, const float* log_std, int32_t log_std_rows, float logstd_floor,
                         const float* eps, int64_t n_rows, int32_t k, float* actions, float* logp, float* clipped,
                         msc_stream_t stream) {

@@ -323,5 +323,29 @@ hipError_t launch_meanstd_filter(const float* x, float* out, int64_t E, int32_t 
 int64_t meanstd_scratch_doubles(int64_t E, int32_t C);
 hipError_t launch_gauss_sample(const float* mean, const float* log_std, int32_t ls_rows, float floor_, const float* eps,
                                int64_t N, int32_t K, float* act, float* logp, float* clipped, hipStream_t st);
+// ppo_loss.hip: the fused PPO loss, statistics and gradients (msc_ppo_loss); lo / hi = 1 -+ clip_param
+// rounded to float32 from float64, as torch.clamp rounds its Python bounds
+struct PpoLossArgs {
+  const float* mean;           // [n][K]
+  const float* log_std;        // [n][K], or [K] when shared
+  const float* values;         // [n]
+  const int64_t* idx;          // [n] batch rows, or nullptr: row i
+  const float* actions;        // [B][K]
+  const float* logp_old;       // [B]
+  const float* advantages;     // [B]
+  const float* value_targets;  // [B]
+  const float* mean_old;       // [B][K] (use_kl)
+  const float* log_std_old;    // [B][K] (use_kl)
+  float* grad_mean;            // [n][K]
+  float* grad_log_std;         // [n][K], or [K] when shared (written by the finalize kernel)
+  float* grad_values;          // [n]
+  int64_t n;
+  int32_t K, use_kl, shared;
+  float lo, hi, vf_clip, c_v, c_e, kl_coeff, beta, inv_n;
+};
+int ppo_loss_rows_per_block(int32_t K);
+int64_t ppo_loss_workspace_bytes(int64_t n, int32_t K);
+hipError_t launch_ppo_loss(const PpoLossArgs& a, int accumulate, float* total, double* stats, void* workspace,
+                           hipStream_t st);
 
 }  // namespace msc

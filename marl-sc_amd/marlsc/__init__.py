@@ -17,6 +17,7 @@ __all__ = [
     "CPPOConfig", "CPPOTrainer", "CentralizedRolloutEnv", "CentralizedActorCritic",
     "RandomPolicy", "ConstantPolicy", "BaseStockPolicy", "AdaptiveBaseStockPolicy", "newsvendor_levels",
     "rollout_episodes", "calibrate_demand", "validation_sweep", "evaluate_levels", "optimize_levels",
+    "fused_ppo_loss",
 ]
 
 _BASELINES = ("RandomPolicy", "ConstantPolicy", "BaseStockPolicy", "AdaptiveBaseStockPolicy", "newsvendor_levels",
@@ -36,6 +37,9 @@ def __getattr__(name):  # torch-dependent modules load lazily
     if name in ("CPPOConfig", "CPPOTrainer", "CentralizedRolloutEnv", "CentralizedActorCritic"):
         from . import cppo
         return getattr(cppo, name)
+    if name == "fused_ppo_loss":
+        from .ppo_loss import fused_ppo_loss
+        return fused_ppo_loss
     if name in _BASELINES:
         from . import baselines
         return getattr(baselines, name)

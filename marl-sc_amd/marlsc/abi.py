@@ -99,6 +99,13 @@ class MscGruWeights(C.Structure):
                 ("bo", C.c_void_p)]
 
 
+class MscPpoLossDesc(C.Structure):
+    """msc_ppo_loss_desc (include/marlsc.h): the fused PPO loss's coefficients and switches."""
+    _fields_ = [("clip_param", C.c_double), ("vf_clip_param", C.c_double), ("vf_loss_coeff", C.c_double),
+                ("entropy_coeff", C.c_double), ("kl_coeff", C.c_double), ("hysteretic_beta", C.c_double),
+                ("use_kl", C.c_int32), ("log_std_rows", C.c_int32), ("accumulate_stats", C.c_int32)]
+
+
 def lib() -> C.CDLL:
     """Load libmarlsc.so (built by __graft_entry__.build()). Raises if it is missing."""
     global _LIB
@@ -145,6 +152,10 @@ def lib() -> C.CDLL:
     L.msc_gae_grouped.argtypes = [vp, vp, vp, vp, vp, C.c_int64, C.c_int32, C.c_float, C.c_float, vp, vp, C.c_int32,
                                   vp, vp]
     L.msc_adv_normalize_grouped.argtypes = [vp, C.c_int64, C.c_int32, vp, vp]
+    L.msc_ppo_loss_workspace.argtypes = [C.c_int64, C.c_int32]
+    L.msc_ppo_loss_workspace.restype = C.c_int64
+    L.msc_ppo_loss.argtypes = [P(MscPpoLossDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int64, C.c_int32, vp, vp,
+                               vp, vp, vp, vp, vp]
     L.msc_env_set_episode_counters.argtypes = [vp, vp]
     L.msc_gaussian_sample.argtypes = [vp, vp, C.c_int32, C.c_float, vp, C.c_int64, C.c_int32, vp, vp, vp, vp]
     L.msc_mlp3_w3_layout.argtypes = [C.c_int32]
@@ -197,7 +208,7 @@ def check(rc: int) -> None:
 EXPORTED_SYMBOLS = [
     "msc_env_create", "msc_env_destroy", "msc_env_dims", "msc_env_kernel_choice", "msc_env_set_option", "msc_env_ea_memory", "msc_env_reset", "msc_env_step", "msc_env_generate_demand", "msc_env_set_pipelining", "msc_env_set_chain_priority", "msc_env_set_episode_ahead", "msc_env_set_timing", "msc_env_read_timing", "msc_env_read_timing_ea", "msc_env_work_counters", "msc_env_obs_flat",
     "msc_env_read_state", "msc_env_state_bytes", "msc_env_save_state", "msc_env_load_state", "msc_env_check",
-    "msc_env_set_episode_counters", "msc_gae", "msc_adv_normalize", "msc_gae_grouped", "msc_adv_normalize_grouped", "msc_gaussian_sample", "msc_mlp3_w3_layout", "msc_mlp3_relu_forward", "msc_mlp2_relu_forward",
+    "msc_env_set_episode_counters", "msc_gae", "msc_adv_normalize", "msc_gae_grouped", "msc_adv_normalize_grouped", "msc_ppo_loss_workspace", "msc_ppo_loss", "msc_gaussian_sample", "msc_mlp3_w3_layout", "msc_mlp3_relu_forward", "msc_mlp2_relu_forward",
     "msc_mlp3_relu_forward_sampled", "msc_mlp2_relu_forward_sampled",
     "msc_mlp_musigma_layout", "msc_mlp3_relu_musigma", "msc_mlp2_relu_musigma",
     "msc_mlp_wide_supported", "msc_mlp3_relu_wide", "msc_mlp2_relu_wide", "msc_reward_team_sum",

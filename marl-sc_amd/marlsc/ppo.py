@@ -51,6 +51,7 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from . import dist as mdist
+from .ppo_loss import STAT_KEYS, fused_loss_default, fused_ppo_loss
 from .rollout import (LOG_STD_MIN, PolicyNets, RecurrentAPI, RolloutCollector, RolloutConfig, check_gru_config,
                       check_head_config, fused_actor_sample, gaussian_sample, head_sample, mlp_forward, network_types,
                       split_global_mlp)
@@ -353,8 +354,16 @@ class PPOLearner:
     def kl_coeff(self) -> float:
         return float(np.mean(self.kl_coeffs))
 
-    def __init__(self, module: MultiAgentActorCritic, cfg: PPOConfig, *, seed: int = 0):
+    def __init__(self, module: MultiAgentActorCritic, cfg: PPOConfig, *, seed: int = 0,
+                 fused_loss: Optional[bool] = None):
+        """fused_loss: the loss, its statistics and its gradients from the msc_ppo_loss kernel
+        (marlsc/ppo_loss.py) instead of ppo_loss under autograd; None reads MSC_FUSED_LOSS (default off).
+        It needs the module on a CUDA device and raises RuntimeError otherwise."""
         self.module, self.cfg = module, cfg
+        self.fused_loss = fused_loss_default() if fused_loss is None else bool(fused_loss)
+        if self.fused_loss and next(module.parameters()).device.type != "cuda":
+            raise RuntimeError("PPOLearner(fused_loss=True): the fused PPO loss is a HIP kernel and needs the module "
+                               f"on a CUDA device, not {next(module.parameters()).device}")
         self.opt = torch.optim.Adam(module.parameters(), lr=cfg.lr_at(0))
         # RLlib keeps one adaptive KL coefficient per module
         self.kl_coeffs = [float(cfg.kl_coeff)] * len(module.policies)
@@ -458,6 +467,8 @@ class PPOLearner:
         else:
             streams = [_CyclicRows(r, min(mb, r.numel()), self.gen) for r in self._module_rows(S, W, obs.device)]
         self.last_minibatch_sizes = [st.mb for st in streams]
+        if self.fused_loss:
+            return self._update_fused(obs, seq, flat, streams)
         acc: Dict[str, float] = {}
         kl_sum = [0.0] * len(streams)
         n = 0
@@ -491,6 +502,8 @@ class PPOLearner:
                 acc[k] = acc.get(k, 0.0) + float(v)
             n += 1
         out = {k: v / max(n, 1) for k, v in acc.items()}
+        # (this tail -- step count, KL all-reduce, adaptive coefficient, learning rate -- has a twin in
+        # _finish_update for the fused path; the default path keeps its own lines: change both together)
         out["num_minibatch_steps"] = n
         if cfg.use_kl_loss:  # RLlib's adaptive KL coefficient, per module
             if self.world > 1:  # the ranks' mean KL: every rank keeps the same coefficients
@@ -498,6 +511,59 @@ class PPOLearner:
                 dist.all_reduce(t, op=dist.ReduceOp.SUM)
                 kl_sum = [float(x) / self.world for x in t.tolist()]
             for j in range(len(streams)):
+                kl = kl_sum[j] / max(n, 1)
+                if kl > 2.0 * cfg.kl_target:
+                    self.kl_coeffs[j] *= 1.5
+                elif kl < 0.5 * cfg.kl_target:
+                    self.kl_coeffs[j] *= 0.5
+            out["kl_coeff"] = float(np.mean(self.kl_coeffs))
+        out["learning_rate"] = self.opt.param_groups[0]["lr"]
+        return out
+
+    def _update_fused(self, obs: torch.Tensor, seq, flat: Dict[str, torch.Tensor], streams) -> Dict[str, float]:
+        """update()'s minibatch loop with the fused loss: the kernel gathers rows `idx` of the flat batch
+        columns itself, and every module's statistics (its KL sum among them) add up in one device f64
+        buffer [modules, 5] that the host reads once, after the last step."""
+        cfg, m = self.cfg, self.module
+        dev_stats = torch.zeros((len(streams), len(STAT_KEYS)), dtype=torch.float64, device=obs.device)
+        n = 0
+        while min(st.covered for st in streams) < max(1, int(cfg.num_epochs)):
+            total = None
+            for j, (pol, st) in enumerate(zip(m.policies, streams)):
+                idx = st.next()
+                if seq is not None:
+                    mean, log_std, values, idx = self._seq_forward(pol, obs, seq, idx)
+                else:
+                    mean, log_std, values = self._forward(pol, obs, idx)
+                loss, _ = fused_ppo_loss(cfg, mean, log_std, values, flat, idx, self.kl_coeffs[j], stats=dev_stats[j])
+                total = loss if total is None else total + loss
+            self.opt.zero_grad(set_to_none=True)
+            total.backward()
+            allreduce_grads([p for p in m.parameters() if p.grad is not None])
+            if cfg.grad_clip:
+                for pol in m.policies:  # each module's gradients by its own global norm
+                    ps = [p for p in pol.parameters() if p.grad is not None]
+                    if ps:
+                        torch.nn.utils.clip_grad_norm_(ps, cfg.grad_clip)
+            self.opt.step()
+            n += 1
+        host = dev_stats.cpu()  # the one read of the update
+        keys = ["policy_loss", "vf_loss", "entropy"] + (["mean_kl"] if cfg.use_kl_loss else []) + ["total_loss"]
+        out = {k: float(host[:, STAT_KEYS.index(k)].sum()) / len(streams) / max(n, 1) for k in keys}
+        return self._finish_update(out, n, [float(x) for x in host[:, STAT_KEYS.index("mean_kl")]], obs.device)
+
+    def _finish_update(self, out: Dict[str, float], n: int, kl_sum: List[float], device) -> Dict[str, float]:
+        """The tail of update() for the fused path: step count, RLlib's adaptive KL coefficient per module,
+        learning rate. It restates update()'s own last lines, which stay where they are so that the
+        default path is untouched: change both together."""
+        cfg = self.cfg
+        out["num_minibatch_steps"] = n
+        if cfg.use_kl_loss:
+            if self.world > 1:  # the ranks' mean KL: every rank keeps the same coefficients
+                t = torch.tensor(kl_sum, dtype=torch.float64, device=device)
+                dist.all_reduce(t, op=dist.ReduceOp.SUM)
+                kl_sum = [float(x) / self.world for x in t.tolist()]
+            for j in range(len(kl_sum)):
                 kl = kl_sum[j] / max(n, 1)
                 if kl > 2.0 * cfg.kl_target:
                     self.kl_coeffs[j] *= 1.5

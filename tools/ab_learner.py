@@ -1,0 +1,178 @@
+"""A/B of the learner's minibatch step with the torch loss (marlsc/ppo.py:ppo_loss under autograd, the default)
+and with the fused loss kernel (msc_ppo_loss, PPOLearner(fused_loss=True), opt-in):
+  step:  one minibatch step as PPOLearner.update runs it -- gather, forward, loss, backward, gradient clip,
+         Adam, and the per-step statistics (the torch path reads them on the host every step, the fused path
+         adds them up on the device);
+  loss:  the loss with its backward alone, from given network outputs to their gradients (torch: the v[idx]
+         gathers, ppo_loss, backward; fused: fused_ppo_loss, backward), no statistic read on the host.
+Shapes: the reference ippo.yaml networks (actor / critic [256], local observations) and the mappo.yaml networks
+(actor [256, 256], global critic [64, 64], KL term on) with the C3 observation width and K = 5, 8 agents
+sharing one policy; a minibatch of 800 rows out of an 8,000-step batch (64,000 rows), and one of 262,144 rows
+(32,768 envs x 8 agents, the whole batch).
+The two variants are alternated in one process after a warm-up; each sample is one step between two device
+events, the device idle before the first (synchronised). Medians, the 5th .. 95th percentile and the range.
+
+  python tools/ab_learner.py [--rounds 100] [--rounds-large 20] [--warmup 10] [--out profiles/ppo_loss/ab_learner.txt]
+  python tools/ab_learner.py --count-launches   # a few steps of each variant at 800 rows, for a kernel trace"""
+import argparse
+import json
+import sys
+from pathlib import Path
+
+import numpy as np
+import torch
+import yaml
+
+REPO = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(REPO / "marl-sc_amd"))
+
+
+def _local_obs_dim() -> int:
+    from marlsc import load_environment_config
+    from marlsc.spec import EnvSpec
+    cfg = load_environment_config(str(REPO / "config_files/environments/env_c3_8wh64r5sku.yaml"), allow_nr_ne_nw=True)
+    return EnvSpec.from_config(cfg, {"include_warehouse_id": True}).local_obs_dim
+
+
+def _setup(name: str, S: int, W: int, L: int, K: int):
+    """(cfg, module, batch [S, W, ...]) for config_files/algorithms/<name>.yaml with a shared policy."""
+    from marlsc.ppo import MultiAgentActorCritic, PPOConfig, gaussian_logp
+    cfg = PPOConfig.from_algorithm_config(yaml.safe_load(open(REPO / f"config_files/algorithms/{name}.yaml")))
+    torch.manual_seed(0)
+    m = MultiAgentActorCritic(W, L, L * W, K, cfg.rollout_config(), True).cuda()
+    obs = torch.randn(S, W, L, device="cuda")
+    with torch.no_grad():
+        mean = torch.cat([m.policies[0].actor(o) for o in obs.split(4096)])
+        ls = torch.clamp(m.policies[0].log_std, min=m.rc.logstd_floor).expand_as(mean).contiguous()
+        act = mean + ls.exp() * torch.randn_like(mean)
+        logp = gaussian_logp(act, mean, ls) + 0.1 * torch.randn(S, W, device="cuda")
+    batch = {"actions": act, "logp": logp, "advantages": torch.randn(S, W, device="cuda"),
+             "value_targets": torch.randn(S, W, device="cuda")}
+    if cfg.use_kl_loss:
+        batch["mean_old"], batch["log_std_old"] = mean + 0.02, ls.clone()
+    return cfg, m, obs, batch
+
+
+class Steps:
+    """The two minibatch steps of PPOLearner.update / _update_fused, one module, on fixed rows idx."""
+
+    def __init__(self, cfg, m, obs, batch, idx):
+        from marlsc.ppo import PPOLearner
+        self.cfg, self.m, self.obs, self.idx = cfg, m, obs, idx
+        S, W = obs.shape[0], obs.shape[1]
+        self.flat = {k: v.reshape(S * W, *v.shape[2:]) for k, v in batch.items()}
+        self.learner = PPOLearner(m, cfg, seed=0, fused_loss=False)
+        self.dev_stats = torch.zeros(5, dtype=torch.float64, device="cuda")
+        self.pol = m.policies[0]
+        self.params = [p for p in self.pol.parameters()]
+
+    def _finish(self, total):
+        self.learner.opt.zero_grad(set_to_none=True)
+        total.backward()
+        if self.cfg.grad_clip:
+            torch.nn.utils.clip_grad_norm_([p for p in self.params if p.grad is not None], self.cfg.grad_clip)
+        self.learner.opt.step()
+
+    def torch_step(self):
+        from marlsc.ppo import ppo_loss
+        b = {k: v[self.idx] for k, v in self.flat.items()}
+        mean, log_std, values = self.learner._forward(self.pol, self.obs, self.idx)
+        loss, sts = ppo_loss(self.cfg, mean, log_std, values, b, 0.2)
+        kl = float(sts["mean_kl"].detach()) if "mean_kl" in sts else 0.0
+        mstats = {k: v.detach() for k, v in sts.items()}
+        self._finish(loss)
+        return kl + sum(float(v) for v in mstats.values())
+
+    def fused_step(self):
+        from marlsc.ppo_loss import fused_ppo_loss
+        mean, log_std, values = self.learner._forward(self.pol, self.obs, self.idx)
+        loss, _ = fused_ppo_loss(self.cfg, mean, log_std, values, self.flat, self.idx, 0.2, stats=self.dev_stats)
+        self._finish(loss)
+
+    def outputs(self):
+        with torch.no_grad():
+            mean, log_std, values = self.learner._forward(self.pol, self.obs, self.idx)
+        return [t.detach().clone().requires_grad_() for t in (mean, log_std[0], values)]
+
+    def torch_loss(self, leaves):
+        from marlsc.ppo import ppo_loss
+        mean, ls, values = leaves
+        b = {k: v[self.idx] for k, v in self.flat.items()}
+        ppo_loss(self.cfg, mean, ls.expand_as(mean), values, b, 0.2)[0].backward()
+
+    def fused_loss(self, leaves):
+        from marlsc.ppo_loss import fused_ppo_loss
+        mean, ls, values = leaves
+        fused_ppo_loss(self.cfg, mean, ls, values, self.flat, self.idx, 0.2, stats=self.dev_stats)[0].backward()
+
+
+def _time(variants, rounds, warmup):
+    times = {k: [] for k in variants}
+    for _ in range(warmup):
+        for fn in variants.values():
+            fn()
+    for _ in range(rounds):
+        for k, fn in variants.items():
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            times[k].append(e0.elapsed_time(e1) * 1e3)  # us
+    return {k: np.asarray(v) for k, v in times.items()}
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=100)
+    ap.add_argument("--rounds-large", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--out", type=str, default=None)
+    ap.add_argument("--count-launches", action="store_true",
+                    help="run 10 torch steps, then 10 fused steps of the ippo networks at 800 rows and exit")
+    args = ap.parse_args()
+    W, K, L = 8, 5, _local_obs_dim()
+    if args.count_launches:
+        cfg, m, obs, batch = _setup("ippo", 8000, W, L, K)
+        st = Steps(cfg, m, obs, batch, torch.randperm(8000 * W, device="cuda")[:800])
+        for fn in (st.torch_step, st.fused_step):
+            for _ in range(10):
+                fn()
+            torch.cuda.synchronize()
+        return 0
+    lines = [f"device: {torch.cuda.get_device_name(0)}   warmup {args.warmup}, variants alternated, one step per sample, us",
+             f"observation width {L} (C3, with the warehouse one-hot), K = {K}, {W} agents on one shared policy"]
+    results = []
+    for name in ("ippo", "mappo"):
+        for S, rows, rounds in ((8000, 800, args.rounds), (32768, 32768 * W, args.rounds_large)):
+            cfg, m, obs, batch = _setup(name, S, W, L, K)
+            st = Steps(cfg, m, obs, batch, torch.randperm(S * W, device="cuda")[:rows])
+            leaves = st.outputs()
+            t = _time({"step_torch": st.torch_step, "step_fused": st.fused_step}, rounds, args.warmup)
+            t.update(_time({"loss_torch": lambda: st.torch_loss(leaves), "loss_fused": lambda: st.fused_loss(leaves)},
+                           rounds, args.warmup))
+            res = {"config": name, "rows": rows, "rounds": rounds}
+            lines.append(f"{name}.yaml networks, minibatch of {rows} rows (batch {S * W} rows), {rounds} rounds")
+            for k, v in t.items():
+                res[k] = {"median_us": float(np.median(v)), "p05_us": float(np.percentile(v, 5)),
+                          "p95_us": float(np.percentile(v, 95)), "min_us": float(v.min()), "max_us": float(v.max())}
+                lines.append(f"  {k:11s} median {res[k]['median_us']:9.1f}   p05 {res[k]['p05_us']:9.1f}   p95 "
+                             f"{res[k]['p95_us']:9.1f}   range {res[k]['min_us']:.1f} .. {res[k]['max_us']:.1f}")
+            for kind in ("step", "loss"):
+                res[f"{kind}_torch_over_fused"] = res[f"{kind}_torch"]["median_us"] / res[f"{kind}_fused"]["median_us"]
+                lines.append(f"  {kind}: torch / fused = {res[f'{kind}_torch_over_fused']:.3f}")
+            results.append(res)
+            del st, leaves, cfg, m, obs, batch
+            torch.cuda.empty_cache()
+    text = "\n".join(lines) + "\n"
+    print(text)
+    print(json.dumps(results))
+    if args.out:
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.out).write_text(text)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
