@@ -179,8 +179,7 @@ int msc_env_dims(const msc_env* env, int64_t* n_envs, int32_t* n_agents, int32_t
  * runs, chosen at create time from its shape and the MSC_* knobs. Writes up to n of
  * {alloc (0 lane, 1 group, 2 scan), envs sorted by order count, phase A fused, phase C fused,
  *  group kernel cost tables in LDS, lane-group width, episode-ahead slots, demand (0 unit parser,
- *  5 park4, 7 split parser, 8 f32-ring parser, 9 demand_v3), equal sampler parameters (UNI)}; returns the
- *  count written. */
+ *  9 demand_v3 where it applies), equal sampler parameters (UNI)}; returns the count written. */
 int msc_env_kernel_choice(const msc_env* env, int32_t* out, int32_t n);
 
 /* Kernel-form options of a handle that change no result (diagnostic / tuning; no reference

@@ -393,20 +393,6 @@ int msc_env_create(const msc_env_desc* d, int device, int64_t n_envs, uint32_t b
     c.uni_thr_o = enlam_o[0];
     c.uni_thr_m = p_skip[0];
     c.uni_thr_q = enlam_q[0];
-    // demand_v2_kernel (demand_v2.hip): its f32 chain decides "prod > exp(-lambda)" only outside a
-    // band of relative width 2^-16 around the threshold (both bounds rounded outward to f32); the SKU
-    // draw U = k 2^-53 < p <=> k < ceil(p 2^53), exact on the integer
-    auto f_up = [](double v) { float f = (float)v; return (double)f < v ? nextafterf(f, INFINITY) : f; };
-    auto f_dn = [](double v) { float f = (float)v; return (double)f > v ? nextafterf(f, -INFINITY) : f; };
-    // (MSC_V2_BAND=b widens the band to 2^-b, b in [2, 16]: tests drive the exact recomputation with it)
-    int band = 16;
-    if (const char* vb = getenv("MSC_V2_BAND")) band = atoi(vb) >= 2 && atoi(vb) <= 16 ? atoi(vb) : band;
-    const double bw = ldexp(1.0, -band);
-    c.v2_thr[0] = f_up(enlam_o[0] * (1.0 + bw));
-    c.v2_thr[1] = f_dn(enlam_o[0] * (1.0 - bw));
-    c.v2_thr[2] = f_up(enlam_q[0] * (1.0 + bw));
-    c.v2_thr[3] = f_dn(enlam_q[0] * (1.0 - bw));
-    c.v2_k53 = (uint64_t)ceil(ldexp(p_sku[0] < 2.0 ? p_sku[0] : 2.0, 53));
   } else if (d->demand_type == MSC_DEMAND_EMPIRICAL) {
     const int rows = d->trace_n_rows;
     if (rows < d->episode_length) return set_err(-1, "trace has %d timesteps < episode_length %d", rows, d->episode_length);
@@ -431,28 +417,14 @@ int msc_env_create(const msc_env_desc* d, int device, int64_t n_envs, uint32_t b
   c.order_cap = order_cap;
   {
     // A/B knobs (timing experiments only; results are identical)
+    // MSC_DEMAND_IMPL: "v3" (9, the default) is the short-round unit parser (demand_v3.hip) where the
+    // sampler's parameters are equal in every region and SKU and the unit parser otherwise; "unit" (0)
+    // forces the unit parser (C3 demand 0.787 -> 0.758 ms, C2 205 -> 208.7 M with v3,
+    // profiles/r06/ab_demand_v3.txt). The forms that lost their A/Bs are gone.
     const char* impl = getenv("MSC_DEMAND_IMPL");
-    // default (0): the unit-per-round parser; "ab" the split chain / bookkeeper parser
-    // (demand_ab_kernel: measured slower), "park4" the round-1 parser
-    // default (9): the short-round unit parser (demand_v3.hip) where the sampler's parameters are equal
-    // in every region and SKU, the unit parser otherwise (0, "unit" forces it; C3 demand 0.787 -> 0.758
-    // ms, C2 205 -> 208.7 M, profiles/r06/ab_demand_v3.txt)
-    c.demand_impl = !impl ? 9 : strcmp(impl, "park4") == 0 ? 5 : strcmp(impl, "ab") == 0 ? 7
-                  : strcmp(impl, "v2") == 0 ? 8 : strcmp(impl, "v3") == 0 ? 9 : 0;
-    // demand_v2_kernel's generator refill per chunk (positions per lane; the parser consumes ~18 at
-    // 8 x 64 x 5): MSC_V2_QUOTA
-    c.v2_quota = 20;
-    if (const char* vq = getenv("MSC_V2_QUOTA")) c.v2_quota = atoi(vq) >= 8 && atoi(vq) <= 64 ? atoi(vq) : c.v2_quota;
-    const char* gen = getenv("MSC_DEMAND_GEN");
-    // (5 and 7: A/B instantiations for 5 SKUs only, more generator waves per 64 envs)
-    c.demand_gen = gen && ((atoi(gen) >= 1 && atoi(gen) <= 3) || (K == 5 && (atoi(gen) == 5 || atoi(gen) == 7))) ? atoi(gen) : 3;
-    const char* v = getenv("MSC_DEMAND_EPW");
-    const int x = v ? atoi(v) : 64;
-    c.epw_dem = x == 16 || x == 32 || x == 64 ? x : 64;
-    const char* pm = getenv("MSC_PARK_MIN");
-    c.park_min = pm && atoi(pm) >= 1 && atoi(pm) <= 64 ? atoi(pm) : 32;
-    const char* prot = getenv("MSC_PARSER_ROT");
-    c.parser_rot = prot ? atoi(prot) : 0;
+    if (impl && strcmp(impl, "v3") != 0 && strcmp(impl, "unit") != 0)
+      return set_err(-1, "MSC_DEMAND_IMPL=%s: accepted values are v3 (the default) and unit", impl);
+    c.demand_impl = impl && strcmp(impl, "unit") == 0 ? 0 : 9;
     // step_c observation staging when the block's stage fits (C3: 8 x 64 x 35 floats = 70 KiB)
     // staged in two phases of ceil(W / 2) agents: half the LDS, so two step_c blocks fit beside the
     // pipelined demand kernel's (C3 MAPPO rollout 1.19 -> 1.14 ms per step; profiles/r03/ab_stage_phases.txt)

@@ -1,6 +1,6 @@
 // demand_common.hpp -- pieces shared by the Poisson demand kernels (env_kernels.hip:
-// demand_unit_kernel / demand_park4_kernel; demand_ab.hip: demand_ab_kernel): the PCG64 state I/O of
-// the env's demand stream, the generator ring geometry and refill quota, the parser states, and the
+// demand_unit_kernel; demand_v3.hip: demand_v3_kernel; demand_seq.hip: demand_seq_kernel): the PCG64
+// state I/O of the env's demand stream, the generator ring geometry and refill quota, the parser states, and the
 // episode-ahead root derivation.
 #pragma once
 #include <hip/hip_runtime.h>

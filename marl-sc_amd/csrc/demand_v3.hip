@@ -283,16 +283,8 @@ __global__ __launch_bounds__(BS * (1 + G)) __attribute__((amdgpu_waves_per_eu(MS
 
 bool demand_v3_supported(const EnvConst& c) {
   // (record strides NV * E * 16 bytes below 2^32: the address multiply-add is 32 x 32 bits)
-  return c.demand_uni != 0 && c.demand_ptrs == 0 && c.K >= 1 && c.K <= UD && c.K <= 8 && c.epw_dem == BS &&
+  return c.demand_uni != 0 && c.demand_ptrs == 0 && c.K >= 1 && c.K <= UD && c.K <= 8 &&
          (uint64_t)c.E * 32u < (1ull << 32);
-}
-
-// the alternative Poisson demand kernels selected by c.demand_impl (8: demand_v2.hip, 9: this file);
-// hipErrorNotSupported when the handle's sampler has no such form (the caller runs the unit parser)
-hipError_t launch_demand_alt(const EnvConst& c, const DevEnv* d, hipStream_t st, const EaLaunch* ea) {
-  if (c.demand_impl == 9 && demand_v3_supported(c)) return launch_demand_v3(c, d, st, ea);
-  if (c.demand_impl == 8 && demand_v2_supported(c)) return launch_demand_v2(c, d, st, ea);
-  return hipErrorNotSupported;
 }
 
 template <int K>

@@ -30,13 +30,9 @@ struct EnvConst {
   int32_t W, K, R, T, Lmax, RING, F, L, order_cap;
   int32_t action_type, lead_type, dev_per_sku, lost_type, scope, norm, wid, num_eval, max_wh;
   int32_t demand_type, init_type, init_min, init_max, hold_per_sku, pen_per_sku, tr_rows;
-  int32_t demand_impl;  // 0 = generator waves + unit-per-round parser (default); 5 = park4 (A/B)
-  int32_t demand_gen;   // generator waves per block of the split demand kernel (1, 2 or 3; 5 / 7 A/B at 5 SKUs)
-  int32_t park_min;     // parked lanes that trigger a settle pass of the demand parser (MSC_PARK_MIN)
-  int32_t parser_rot;   // which wave of a demand block parses: (wave + rot(block)) % (1 + G) == 0 (A/B knob)
+  int32_t demand_impl;  // Poisson demand kernel: 9 = demand_v3_kernel where it applies (default), 0 = demand_unit_kernel
   int32_t obs_stage;    // 1: step_c stages each wave's observations in LDS and writes them coalesced
   int32_t obs_ring_reg; // 1: step_a / step_c (<= 8 warehouses) read the pending ring into registers before their stores
-  int32_t epw_dem;      // envs per 64-lane block of the demand kernel (64, 32 or 16; see launch_demand)
   int32_t shared_home;  // 1: some region is the home region of two or more warehouses
   int32_t demand_uni;   // 1: Poisson parameters equal across regions (demand_unit_kernel<UNI>)
   int32_t alloc_impl;   // phase B: 0 = one env per lane (alloc_lane_kernel); 1 = one env per lane group (step_b_kernel)
@@ -59,12 +55,6 @@ struct EnvConst {
   int64_t ea_cap;       // episode-ahead demand: order records per (slot, env) episode
   double scale, alpha, hold_scalar, pen_scalar;
   double uni_thr_o, uni_thr_m, uni_thr_q;  // demand_uni: exp(-lambda_orders), p_skip, exp(-lambda_quantity)
-  // demand_v2_kernel (demand_v2.hip, f32 ring): the f32 chain's decision thresholds around exp(-lambda)
-  // {orders hi, orders lo, quantity hi, quantity lo}, the exact SKU-draw bound ceil(p * 2^53) on the
-  // 53-bit draw, and the generators' refill quota per chunk
-  float v2_thr[4];
-  uint64_t v2_k53;
-  int32_t v2_quota;
   const MSC_G double* act_param;   // [K]
   const MSC_G int32_t* init_vals;  // [W*K]
   const MSC_G double* hold;        // [K]
@@ -216,21 +206,13 @@ constexpr int SORT_BUCKETS = 1024;
 // alloc_kernels.hip
 hipError_t launch_alloc_lane(const EnvConst& c, const DevEnv* d, const StepIO& io, hipStream_t st);
 hipError_t launch_obs_flat(const EnvConst& c, const float* obs, float* flat, hipStream_t st);
-size_t demand_lds_bytes(const EnvConst& c);  // per block of the production demand kernel
-// demand_ab.hip: the split-parser Poisson demand kernel (equal sampler parameters in every region)
-bool demand_ab_supported(const EnvConst& c);
+// demand_seq.hip: the sequential Poisson demand sampler (a rate >= 10, or more than 8 SKUs)
 hipError_t launch_demand_seq(const EnvConst& c, const DevEnv* d, hipStream_t st, const EaLaunch* ea);
 hipError_t launch_poisson_draws(uint64_t* state, const PtrsConst* ptrs, const double* enlam, int64_t n_lam, int64_t n,
                                 int64_t* out, hipStream_t st);
-hipError_t launch_demand_ab(const EnvConst& c, const DevEnv* d, hipStream_t st, const EaLaunch* ea);
-// demand_v2.hip: the f32-ring Poisson demand kernel (equal sampler parameters, <= 8 SKUs)
-bool demand_v2_supported(const EnvConst& c);
-hipError_t launch_demand_v2(const EnvConst& c, const DevEnv* d, hipStream_t st, const EaLaunch* ea);
-// demand_v3.hip: the unit parser with a shorter round (equal sampler parameters, <= 8 SKUs), and the
-// dispatcher of the alternative demand kernels (c.demand_impl 8 / 9)
+// demand_v3.hip: the unit parser with a shorter round (equal sampler parameters, <= 8 SKUs)
 bool demand_v3_supported(const EnvConst& c);
 hipError_t launch_demand_v3(const EnvConst& c, const DevEnv* d, hipStream_t st, const EaLaunch* ea);
-hipError_t launch_demand_alt(const EnvConst& c, const DevEnv* d, hipStream_t st, const EaLaunch* ea);
 hipError_t launch_gen_draws(int G, const uint64_t* state, const uint64_t* inc, int64_t n, uint64_t* out,
                             uint64_t* state_out, hipStream_t st);
 int order_record_vec4(int K);

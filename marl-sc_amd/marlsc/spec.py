@@ -243,7 +243,7 @@ class EnvSpec:
                              f"(max {abi.MAX_W}/{abi.MAX_K}/{abi.MAX_R})")
         if self.demand_type == "poisson":
             # rates >= 10 take numpy's PTRS branch (demand_sampler.py:138,153 -> Generator.poisson):
-            # the library's sequential sampler (csrc/demand_ab.hip, demand_seq_kernel)
+            # the library's sequential sampler (csrc/demand_seq.hip, demand_seq_kernel)
             if not (np.all(self.lambda_orders > 0) and np.all(self.lambda_quantity > 0)):
                 raise ValueError("Poisson rates must be positive (PositiveFloat, schema.py:191)")
             if np.any(self.lambda_orders >= 1e6) or np.any(self.lambda_quantity >= 20000):

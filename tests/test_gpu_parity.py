@@ -91,6 +91,8 @@ def test_gpu_matches_reference_golden(name):
     spec = spec_of(d, meta)
     E, S = meta["n_envs"], meta["n_steps"]
     env = _vec(spec, E, env_seeds=meta["env_seeds"])
+    if name == "variant_b":  # Poisson parameters that vary by region: the unit parser's table form
+        assert env.kernel_choice()["demand_uni"] == 0
     np.testing.assert_array_equal(_np(env.reset()), d["reset_obs"][:, 0])
     st = env.read_state()
     np.testing.assert_array_equal(st["inventory"], d["reset_inventory"][:, 0])
@@ -204,18 +206,6 @@ def test_set_option_mid_run_matches_default(monkeypatch):
             b.set_option(key, val)
 
 
-@pytest.mark.parametrize("gen,ea", [(1, "0"), (2, "0"), (5, "0"), (7, "0"), (5, "1"), (7, "1")])
-def test_demand_generator_waves_vs_oracle(monkeypatch, gen, ea):
-    # the Poisson demand kernel with 1 / 2 / 5 / 7 generator waves per 64 envs (MSC_DEMAND_GEN; every
-    # other test runs the default 3), per step and episode-ahead, in lockstep with the oracle at the
-    # BASELINE 8 x 64 x 5 shape across an episode boundary (5 and 7: A/B instantiations at 5 SKUs)
-    monkeypatch.setenv("MSC_DEMAND_GEN", str(gen))
-    monkeypatch.setenv("MSC_EA", ea)
-    cfg = make_synthetic_env_config(8, 64, 5, episode_length=20)
-    spec = EnvSpec.from_config(cfg, {"include_warehouse_id": True})
-    _lockstep(spec, 192, 45, seed=gen, check_every=5)
-
-
 @pytest.mark.usefixtures("alloc_impl_lpe")
 def test_c5_shape_vs_oracle():
     cfg = make_synthetic_env_config(16, 256, 5, episode_length=12)
@@ -254,7 +244,9 @@ def test_c5_bench_geometry_vs_oracle_8192(monkeypatch):
 @pytest.mark.usefixtures("alloc_impl")
 def test_variants_vs_oracle_many_envs(name):
     d, meta = load(name)
-    _lockstep(spec_of(d, meta), 300, 70, seed=3, check_every=7)
+    env, _ = _lockstep(spec_of(d, meta), 300, 70, seed=3, check_every=7)
+    if name == "variant_b":  # (as above: the unit parser with per-region thresholds, over several blocks)
+        assert env.kernel_choice()["demand_uni"] == 0
 
 
 def test_generate_demand_split_equals_fused():
@@ -768,22 +760,11 @@ def test_poisson_ptrs_device_known_answers():
 def test_ptrs_rates_env_vs_oracle(monkeypatch, ea, lo, lq):
     # Poisson rates >= 10 (numpy's PTRS branch) in the env, quantities
     # (lambda_q = 12) or order counts (lambda_o = 11), against the oracle in lockstep, with
-    # per-step and episode-ahead demand (the sequential sampler, csrc/demand_ab.hip)
+    # per-step and episode-ahead demand (the sequential sampler, csrc/demand_seq.hip)
     monkeypatch.setenv("MSC_EA", ea)
     cfg = make_synthetic_env_config(4, 16, 3, episode_length=7, lambda_orders=lo, lambda_quantity=lq)
     spec = EnvSpec.from_config(cfg, {"include_warehouse_id": True})
     _lockstep(spec, 96, 17, seed=4, check_every=2)
-
-
-@pytest.mark.parametrize("ea", ["0", "1"])
-def test_split_parser_demand_vs_oracle(monkeypatch, ea):
-    # the split chain / bookkeeper demand parser (MSC_DEMAND_IMPL=ab, csrc/demand_ab.hip; an A/B
-    # variant, measured slower than the default unit parser) against the oracle, per step and episode-ahead
-    monkeypatch.setenv("MSC_DEMAND_IMPL", "ab")
-    monkeypatch.setenv("MSC_EA", ea)
-    cfg = make_synthetic_env_config(8, 64, 5, episode_length=9)
-    spec = EnvSpec.from_config(cfg, {"include_warehouse_id": True})
-    _lockstep(spec, 192, 21, seed=6, check_every=4)
 
 
 @pytest.mark.parametrize("impl", ["v3", "unit"])
@@ -802,48 +783,39 @@ def test_demand_v3_vs_oracle(monkeypatch, ea, impl):
     assert env.kernel_choice()["demand_impl"] == (9 if impl == "v3" else 0)
 
 
-@pytest.mark.parametrize("ea", ["0", "1"])
-@pytest.mark.parametrize("band,quota", [(None, None), ("3", None), (None, "8"), (None, "40")])
-def test_demand_v2_vs_oracle(monkeypatch, ea, band, quota):
-    # the f32-ring demand kernel (csrc/demand_v2.hip): f32 draws with the SKU draw in the sign bit, a
-    # 128-position ring, the f32 Poisson chain decided outside a band around exp(-lambda) and the exact
-    # recomputation (jump-ahead + numpy's f64 chain) inside it; per step and episode-ahead, in lockstep
-    # with the oracle across episode boundaries. band 2^-3 sends a large share of the Poisson rounds
-    # through the exact path; quota 8 / 40 exercise the generators' top-up barrier and a full ring
-    monkeypatch.setenv("MSC_DEMAND_IMPL", "v2")
-    monkeypatch.setenv("MSC_EA", ea)
-    if band:
-        monkeypatch.setenv("MSC_V2_BAND", band)
-    if quota:
-        monkeypatch.setenv("MSC_V2_QUOTA", quota)
-    cfg = make_synthetic_env_config(8, 64, 5, episode_length=9)
-    spec = EnvSpec.from_config(cfg, {"include_warehouse_id": True})
-    env, _ = _lockstep(spec, 192, 21, seed=7, check_every=4)
-    assert env.kernel_choice()["demand_impl"] == 8
-
-
-@pytest.mark.parametrize("impl", ["v2", "v3"])
+@pytest.mark.parametrize("impl", ["unit", "v3"])
 @pytest.mark.parametrize("K,lo,lq,p", [(1, 4.0, 5.0, 0.667), (3, 2.5, 9.5, 0.3), (8, 1.5, 9.9, 1.0), (6, 9.9, 0.4, 0.9)])
-def test_demand_v2_shapes_and_rates_vs_oracle(monkeypatch, impl, K, lo, lq, p):
-    # the f32-ring kernel (v2) at other SKU counts and rates: lambda 9.5-9.9 (units past 24 draws,
-    # decided exactly), p = 1 (every SKU drawn: the integer bound ceil(p 2^53) = 2^53), tiny quantity
-    # rates; the same shapes through the short-round unit parser (v3, csrc/demand_v3.hip)
+def test_demand_shapes_and_rates_vs_oracle(monkeypatch, impl, K, lo, lq, p):
+    # the fallback unit parser (unit) and the short-round unit parser (v3, csrc/demand_v3.hip) at other
+    # SKU counts and rates: lambda 9.5-9.9 (units that run past one 8-draw round), p = 1 (every SKU
+    # drawn), tiny quantity rates
     monkeypatch.setenv("MSC_DEMAND_IMPL", impl)
     cfg = make_synthetic_env_config(5, 24, K, episode_length=7, lambda_orders=lo, lambda_quantity=lq,
                                     probability_skus=p)
     spec = EnvSpec.from_config(cfg, {"include_warehouse_id": True})
     env, _ = _lockstep(spec, 130, 16, seed=K, check_every=3)
-    assert env.kernel_choice()["demand_impl"] == (8 if impl == "v2" else 9)
+    assert env.kernel_choice()["demand_impl"] == (9 if impl == "v3" else 0)
 
 
-@pytest.mark.parametrize("impl", ["v2", "v3"])
+@pytest.mark.parametrize("impl", ["v3"])
 @pytest.mark.usefixtures("alloc_impl")
-def test_demand_v2_bench_shape_vs_oracle(monkeypatch, impl):
+def test_demand_bench_shape_vs_oracle(monkeypatch, impl):
     # BASELINE configs[2] shape with every allocation kernel, 512 envs, 110 steps (one auto-reset)
     monkeypatch.setenv("MSC_DEMAND_IMPL", impl)
     cfg = make_synthetic_env_config(8, 64, 5)
     spec = EnvSpec.from_config(cfg, {"include_warehouse_id": True})
     _lockstep(spec, 512, 110, seed=11, check_every=10)
+
+
+def test_retired_demand_impl_is_rejected(monkeypatch):
+    # MSC_DEMAND_IMPL accepts v3 and unit; a retired name fails msc_env_create, it does not fall
+    # through to the unit parser
+    from marlsc import abi
+    monkeypatch.setenv("MSC_DEMAND_IMPL", "v2")
+    spec = EnvSpec.from_config(make_synthetic_env_config(4, 16, 3), {"include_warehouse_id": True})
+    with pytest.raises(RuntimeError):
+        _vec(spec, 64)
+    assert b"MSC_DEMAND_IMPL" in abi.lib().msc_last_error()
 
 
 def test_episode_ahead_runtime_switch_stays_exact(monkeypatch):
