@@ -182,6 +182,19 @@ int msc_env_dims(const msc_env* env, int64_t* n_envs, int32_t* n_agents, int32_t
  *  9 demand_v3 where it applies), equal sampler parameters (UNI)}; returns the count written. */
 int msc_env_kernel_choice(const msc_env* env, int32_t* out, int32_t n);
 
+/* The same choice without a handle and without touching a GPU: what msc_env_create would pick for
+ * this descriptor and env count under the current MSC_* knobs, on a device with n_cus compute units
+ * (< 1: 256) and free_bytes of free memory (< 0: the episode-ahead memory fit is not applied).
+ * Validates like msc_env_create (same codes and texts). Writes up to n of: the nine values of
+ * msc_env_kernel_choice in its order, then
+ *  {obs_stage (as the handle starts: its episode-ahead value where that is on), obs_ring_reg, alloc_lpe,
+ *   sort_shift, scan_defer, sc_tab, sc_form, al_psplit, demand_ptrs, order_cap, RING, ea_cap,
+ *   ea_batch, ea_chunk, pipeline, arena bytes / 256, bytes of one order buffer / 256}
+ * (both buffers are 256-byte granular; msc_env_state_bytes = header + arena + one order buffer).
+ * Returns the count written (26 at most), or < 0. */
+int msc_env_plan(const msc_env_desc* desc, int64_t n_envs, int32_t n_cus, int64_t free_bytes, int32_t* out,
+                 int32_t n);
+
 /* Kernel-form options of a handle that change no result (diagnostic / tuning; no reference
  * counterpart). MSC_OPT_STEP_C_FORM: the waves per SIMD the observation kernel is compiled for, 5
  * (default: beside the pipelined demand kernel) or 4 (no register spills; the rollout collector's

@@ -33,6 +33,7 @@
 #include <type_traits>
 
 #include "env.hpp"
+#include "env_plan.hpp"
 #include "kcommon.hpp"
 #include "obs_common.hpp"
 
@@ -99,8 +100,8 @@ struct ScLostLds {
   double lr_wt[64];            // one pass's shares [i % (64 / GW)][w]
 };
 // fused phase C: the per-(SKU, warehouse) inputs of the observation builder, [field][s * GW + w]
-// (aliases the deferred-region block, flushed by then; allocated as the larger of the two)
-constexpr int SC_FC_RING = 4;  // pending-ring slots staged (lead times <= 3)
+// (aliases the deferred-region block, flushed by then; allocated as the larger of the two; the ring
+// slots staged, SC_FC_RING, are with alloc_scan_fuse_supported in env_plan.hpp)
 // (the fields an agent's totals read across its SKU lanes; the ring, history and lead time a lane
 // reads only for its own SKU stay in its registers)
 enum : int { FC_INV, FC_DH, FC_SH, FC_SA, FC_PEND, FC_FC, FC_RM, FC_NF };
@@ -1067,12 +1068,6 @@ size_t alloc_scan_lds_bytes(const EnvConst& c) {
   return (alloc_scan_tab(c, GW) ? sc_tab_bytes(c.R, GW) : 0) + sizeof(int32_t) * ((c.R + 3) & ~3) +
          SC_WAVES * wave_b + SC_WAVES * tail_b;
 }
-// phase C fused into the scan allocator: one slot per lane (<= 8 warehouses), pending rings of at
-// most SC_FC_RING slots
-bool alloc_scan_fuse_supported(int W, int K, int RING) { return W <= 8 && K <= 6 && RING <= SC_FC_RING; }
-// <= 8 warehouses with <= 6 SKUs (one slot per lane), 9-16 warehouses with <= 6 SKUs (two slots
-// above 4 SKUs)
-bool alloc_scan_supported(int W, int K) { return W <= 16 && K <= 6; }
 
 #ifndef MSC_SC_ND
 #define MSC_SC_ND 1  // the fused scan step without step info runs its no-info instantiation

@@ -17,6 +17,7 @@
 
 #include "../../include/marlsc.h"
 #include "env.hpp"
+#include "env_plan.hpp"
 #include "rng.hpp"
 
 using namespace msc;
@@ -74,7 +75,8 @@ struct msc_env {
   int64_t ea_budget = 0, ea_bytes = 0;  // episode-ahead memory budget and bytes allocated (create time)
   bool ea_enabled = false;  // configured: Poisson demand, few envs (or MSC_EA=1), buffers allocated
   bool ea_paused = false;   // msc_env_set_episode_ahead(0): per-step demand until re-enabled
-  int32_t obs_stage_pe = 0, chain_prio_pe = 0;  // step_c staging / chain priority of the per-step path
+  // step_c staging / chain priority of the per-step path and with EA on, both pairs fixed at create
+  int32_t obs_stage_pe = 0, chain_prio_pe = 0, obs_stage_ea = 0, chain_prio_ea = 0;
   bool ea_running = false;
   int64_t ea_n = 0;         // episode (relative to the snapshot) the envs are in
   int ea_cur = -1;          // slot of the current episode, -1: per-step demand
@@ -113,6 +115,23 @@ static void timing_free(msc_env* env) {
   env->tev_step.clear();
   env->tev_ea.clear();
   env->t_cap = env->n_tdem = env->n_tstep = env->n_tea = 0;
+}
+// Everything a handle owns; msc_env_destroy and a failing msc_env_create both end here (members a
+// partial create has not reached yet are null).
+static void env_release(msc_env* env) {
+  for (void* m : {env->tables, env->arena, env->scratch, (void*)env->dev, env->ea_mem})
+    if (m) (void)hipFree(m);
+  for (hipEvent_t e : {env->ev_dem[0], env->ev_dem[1], env->ev_step[0], env->ev_step[1], env->ev_reset, env->ev_snap,
+                       env->ev_chunk})
+    if (e) (void)hipEventDestroy(e);
+  for (int j = 0; j < MSC_EA_MAX_S; j++) {
+    if (env->ev_gen[j]) (void)hipEventDestroy(env->ev_gen[j]);
+    if (env->ev_cons[j]) (void)hipEventDestroy(env->ev_cons[j]);
+  }
+  timing_free(env);
+  if (env->side) (void)hipStreamDestroy(env->side);
+  if (env->ea_stream) (void)hipStreamDestroy(env->ea_stream);
+  delete env;
 }
 // record event `i` (0 = before, 1 = after) of launch n of `v` on `st`, if timing is on
 static hipError_t tmark(const msc_env* env, const std::vector<hipEvent_t>& v, int n, int i, hipStream_t st) {
@@ -243,539 +262,92 @@ int msc_abi_version(void) { return MSC_ABI_VERSION; }
 
 uint32_t msc_seedseq_u32(const uint32_t* words, int32_t n) { return ss_u32(words, n); }
 
-static int feature_dim(const msc_env_desc* d, int Lmax) {
-  const uint32_t f = d->feature_flags;
-  const int K = d->n_skus;
-  int n = 0;
-  if (f & MSC_F_INVENTORY) n += K + ((f & MSC_F_INVENTORY_AGG) ? 1 : 0);
-  if (f & MSC_F_PIPELINE) n += Lmax * K + ((f & MSC_F_PIPELINE_AGG) ? 1 : 0);
-  if (f & MSC_F_INCOMING_HOME) n += K + ((f & MSC_F_INCOMING_HOME_AGG) ? 1 : 0);
-  if (f & MSC_F_SHIPPED_HOME) n += K;
-  if (f & MSC_F_SHIPPED_AWAY) n += K + ((f & MSC_F_SHIPPED_AWAY_AGG) ? 1 : 0);
-  if (f & MSC_F_STOCKOUT) n += K;
-  if (f & MSC_F_ROLLING_MEAN) n += K + ((f & MSC_F_ROLLING_MEAN_AGG) ? 1 : 0);
-  if (f & MSC_F_FORECAST) n += K + ((f & MSC_F_FORECAST_AGG) ? 1 : 0);
-  if (f & MSC_F_DAYS_OF_SUPPLY) n += K;
-  if (f & MSC_F_NET_POSITION) n += K;
-  if (f & MSC_F_DEMAND_VARIABILITY) n += K;
-  if (f & MSC_F_DEMAND_HISTORY) n += MSC_HISTORY * K;
-  return n;
+// the one reader of the create-time MSC_* variables (parsed by env_plan.hpp)
+static EnvKnobs read_env_knobs() {
+  return read_env_knobs(+[](const char* name) -> const char* { return getenv(name); });
 }
 
-// Packs host vectors into one device allocation; returns device pointers by offset.
-struct TablePack {
-  std::vector<char> host;
-  size_t add(const void* p, size_t bytes) {
-    size_t off = (host.size() + 15) & ~size_t(15);
-    host.resize(off + bytes);
-    if (bytes) memcpy(host.data() + off, p, bytes);
-    return off;
-  }
-};
-
+// Builds the handle that plan_env (env_plan.hpp) describes:
+// knobs -> plan -> tables -> arena -> order buffers -> EA buffers -> descriptors -> streams and events.
 int msc_env_create(const msc_env_desc* d, int device, int64_t n_envs, uint32_t base_seed, uint32_t worker_index,
                    int64_t env_index_offset, const uint32_t* env_seeds_host, msc_env** out) {
   if (!d || !out) return set_err(-1, "null argument");
   *out = nullptr;
-  if (d->abi_version != MSC_ABI_VERSION) return set_err(-1, "abi_version %d != %d", d->abi_version, MSC_ABI_VERSION);
-  const int W = d->n_warehouses, K = d->n_skus, R = d->n_regions;
-  if (W < 1 || W > MSC_MAX_W) return set_err(-1, "n_warehouses must be in [1, %d]", MSC_MAX_W);
-  if (K < 1 || K > MSC_MAX_K) return set_err(-1, "n_skus must be in [1, %d]", MSC_MAX_K);
-  if (R < 1 || R > MSC_MAX_R) return set_err(-1, "n_regions must be in [1, %d]", MSC_MAX_R);
-  if (d->episode_length < 1) return set_err(-1, "episode_length must be positive");
-  if (n_envs < 1) return set_err(-1, "n_envs must be positive");
-  if (d->max_splits < 0 || d->max_splits >= W) return set_err(-1, "max_splits must be < n_warehouses=%d", W);
-  const int WK = W * K;
-
-  // lead times -> pipeline horizon and pending ring size
-  int Lmax = 0, lact_max = 0;
-  for (int i = 0; i < WK; i++) {
-    const int elt = d->expected_lead_times[i];
-    if (elt < 1) return set_err(-1, "expected_lead_times must be positive");
-    int dev = 0;
-    if (d->lead_type == MSC_LEAD_STOCHASTIC) dev = d->max_dev_per_sku ? d->max_deviation[i % K] : d->max_deviation[0];
-    if (dev < 0) return set_err(-1, "max_deviation must be non-negative");
-    Lmax = elt > Lmax ? elt : Lmax;
-    lact_max = elt + dev > lact_max ? elt + dev : lact_max;
-  }
-  const int RING = lact_max + 1;
-  if (RING > MAX_RING) return set_err(-1, "max actual lead time %d exceeds %d", lact_max, MAX_RING - 1);
-
-  EnvConst c{};
-  c.W = W; c.K = K; c.R = R; c.T = d->episode_length; c.Lmax = Lmax; c.RING = RING;
-  c.F = feature_dim(d, Lmax);
-  c.L = c.F + (d->include_warehouse_id ? W : 0);
-  c.action_type = d->action_type; c.lead_type = d->lead_type; c.dev_per_sku = d->max_dev_per_sku;
-  c.lost_type = d->lost_type; c.scope = d->reward_scope; c.norm = d->obs_norm; c.wid = d->include_warehouse_id;
-  c.num_eval = d->num_eval_episodes; c.max_wh = d->max_splits + 1; c.demand_type = d->demand_type;
-  c.init_type = d->init_type; c.init_min = d->init_min; c.init_max = d->init_max;
-  c.hold_per_sku = d->holding_per_sku; c.pen_per_sku = d->penalty_per_sku;
-  c.flags = d->feature_flags; c.E = n_envs; c.scale = d->reward_scale; c.alpha = d->lost_alpha;
-  c.hold_scalar = d->holding_per_sku ? 0.0 : d->holding_cost[0];
-  c.pen_scalar = d->penalty_per_sku ? 0.0 : d->penalty_cost[0];
-  if (c.lost_type == MSC_LOST_COST && !(c.alpha > 0)) return set_err(-1, "cost lost-sales alpha must be > 0");
-  if (c.norm == MSC_OBS_MEANSTD && (!d->obs_mean || !d->obs_std)) return set_err(-1, "meanstd needs obs_mean/obs_std");
-  if (d->init_type == MSC_INIT_UNIFORM && (d->init_min < 0 || d->init_min > d->init_max))
-    return set_err(-1, "uniform initial inventory needs 0 <= min <= max");
-
-  // ---- static tables ---------------------------------------------------------------------
-  std::vector<double> zeros_k(K, 0.0), hold(K), pen(K), ofT((size_t)R * W), ovT((size_t)R * W);
-  for (int s = 0; s < K; s++) {
-    hold[s] = d->holding_per_sku ? d->holding_cost[s] : 0.0;
-    pen[s] = d->penalty_per_sku ? d->penalty_cost[s] : 0.0;
-  }
-  for (int w = 0; w < W; w++)
-    for (int r = 0; r < R; r++) {
-      ofT[(size_t)r * W + w] = d->outbound_fixed[(size_t)w * R + r];
-      ovT[(size_t)r * W + w] = d->outbound_variable[(size_t)w * R + r];
-    }
-  std::vector<uint32_t> home_mask(R, 0u);
-  std::vector<int32_t> closest(R, 0), home_of(W, 0);
-  for (int w = 0; w < W; w++) {  // argmin over regions (first minimum), multi_env.py:144
-    int b = 0;
-    for (int r = 1; r < R; r++)
-      if (d->distances[(size_t)w * R + r] < d->distances[(size_t)w * R + b]) b = r;
-    home_mask[b] |= 1u << w;
-    home_of[w] = b;
-  }
-  c.shared_home = 0;
-  for (int r = 0; r < R; r++) c.shared_home |= __builtin_popcount(home_mask[r]) > 1 ? 1 : 0;
-  for (int r = 0; r < R; r++) {  // argmin over warehouses, lost_sales_handler.py:36
-    int b = 0;
-    for (int w = 1; w < W; w++)
-      if (d->distances[(size_t)w * R + r] < d->distances[(size_t)b * R + r]) b = w;
-    closest[r] = b;
-  }
-  std::vector<double> enlam_o(R, 1.0), p_sku(R, 0.0), p_skip(R, 0.0), enlam_q((size_t)R * K, 1.0);
-  std::vector<PtrsConst> ptrs_o(R), ptrs_q((size_t)R * K);
-  int order_cap = 1;
-  int nv = order_record_vec4(K);
-  std::vector<uint4> trec;
-  std::vector<int64_t> toff;
-  if (d->demand_type == MSC_DEMAND_POISSON) {
-    double lam_sum = 0.0;
-    for (int r = 0; r < R; r++) {
-      const double lo = d->lambda_orders[r];
-      // PositiveFloat in the reference schema (schema.py:191); >= 10 is numpy's PTRS branch
-      if (!(lo > 0.0 && lo < 1e6)) return set_err(-1, "lambda_orders[%d]=%g: must be in (0, 1e6)", r, lo);
-      enlam_o[r] = exp(-lo);
-      ptrs_o[r] = ptrs_const_host(lo);
-      if (lo >= 10.0) c.demand_ptrs = 1;
-      if (lo > 0.0 && lo < 10.0 && enlam_o[r] >= 1.0) return set_err(-1, "lambda_orders[%d] too small", r);
-      p_sku[r] = d->probability_skus[r];
-      // random() draws are multiples of 2^-53: U < p <=> U < ceil53(p) <=> !(U > ceil53(p) - 2^-53)
-      p_skip[r] = ldexp(ceil(ldexp(p_sku[r], 53)), -53) - 0x1p-53;
-      lam_sum += lo;
-      for (int s = 0; s < K; s++) {
-        const double lq = d->lambda_quantity[(size_t)r * K + s];
-        // quantities are stored as 16-bit record fields: rates far below 2^16
-        if (!(lq > 0.0 && lq < 20000.0)) return set_err(-1, "lambda_quantity[%d,%d]=%g: must be in (0, 20000)", r, s, lq);
-        enlam_q[(size_t)r * K + s] = exp(-lq);
-        ptrs_q[(size_t)r * K + s] = ptrs_const_host(lq);
-        if (lq >= 10.0) c.demand_ptrs = 1;
-      }
-    }
-    // record capacity per env and step in int64 first: the kernels index records with int32, so a
-    // configuration whose per-step capacity does not fit is rejected here (rates up to 1e6 x 4,096
-    // regions would otherwise wrap the cast)
-    const double cap_d = ceil(lam_sum + 12.0 * sqrt(lam_sum + 1.0) + 64.0);
-    if (!(cap_d <= (double)MSC_ORDER_CAP_MAX))
-      return set_err(-1, "sum of lambda_orders %g: per-step order capacity %.0f exceeds %d records per env", lam_sum,
-                     cap_d, MSC_ORDER_CAP_MAX);
-    order_cap = (int)cap_d;
-    // equal parameters in every region (and SKU): the demand parser's constant-threshold variant
-    c.demand_uni = 1;
-    for (int r = 0; r < R; r++) {
-      c.demand_uni &= enlam_o[r] == enlam_o[0] && p_skip[r] == p_skip[0] ? 1 : 0;
-      for (int s = 0; s < K; s++) c.demand_uni &= enlam_q[(size_t)r * K + s] == enlam_q[0] ? 1 : 0;
-    }
-    if (const char* du = getenv("MSC_DEMAND_UNI")) c.demand_uni &= atoi(du) != 0 ? 1 : 0;
-    c.uni_thr_o = enlam_o[0];
-    c.uni_thr_m = p_skip[0];
-    c.uni_thr_q = enlam_q[0];
-  } else if (d->demand_type == MSC_DEMAND_EMPIRICAL) {
-    const int rows = d->trace_n_rows;
-    if (rows < d->episode_length) return set_err(-1, "trace has %d timesteps < episode_length %d", rows, d->episode_length);
-    const int64_t n_ord = d->trace_offsets[rows];
-    toff.assign(d->trace_offsets, d->trace_offsets + rows + 1);
-    trec.assign((size_t)(n_ord > 0 ? n_ord : 1) * nv, make_uint4(0, 0, 0, 0));
-    for (int64_t j = 0; j < n_ord; j++) {
-      uint16_t* h = reinterpret_cast<uint16_t*>(&trec[(size_t)j * nv]);
-      const int reg = d->trace_regions[j];
-      if (reg < 0 || reg >= R) return set_err(-1, "trace region %d out of range", reg);
-      h[0] = (uint16_t)reg;
-      for (int s = 0; s < K; s++) {
-        const int q = d->trace_quantities[j * K + s];
-        if (q < 0 || q > 65535) return set_err(-1, "trace quantity %d out of range", q);
-        h[1 + s] = (uint16_t)q;
-      }
-    }
-    c.tr_rows = rows;
-  } else {
-    return set_err(-1, "unknown demand_type %d", d->demand_type);
-  }
-  c.order_cap = order_cap;
-  {
-    // A/B knobs (timing experiments only; results are identical)
-    // MSC_DEMAND_IMPL: "v3" (9, the default) is the short-round unit parser (demand_v3.hip) where the
-    // sampler's parameters are equal in every region and SKU and the unit parser otherwise; "unit" (0)
-    // forces the unit parser (C3 demand 0.787 -> 0.758 ms, C2 205 -> 208.7 M with v3,
-    // profiles/r06/ab_demand_v3.txt). The forms that lost their A/Bs are gone.
-    const char* impl = getenv("MSC_DEMAND_IMPL");
-    if (impl && strcmp(impl, "v3") != 0 && strcmp(impl, "unit") != 0)
-      return set_err(-1, "MSC_DEMAND_IMPL=%s: accepted values are v3 (the default) and unit", impl);
-    c.demand_impl = impl && strcmp(impl, "unit") == 0 ? 0 : 9;
-    // step_c observation staging when the block's stage fits (C3: 8 x 64 x 35 floats = 70 KiB)
-    // staged in two phases of ceil(W / 2) agents: half the LDS, so two step_c blocks fit beside the
-    // pipelined demand kernel's (C3 MAPPO rollout 1.19 -> 1.14 ms per step; profiles/r03/ab_stage_phases.txt)
-    c.obs_stage = (size_t)BS * ((c.W * c.L) | 1) * sizeof(float) <= 80 * 1024 ? (c.W >= 2 ? 2 : 1) : 0;
-    // MSC_OBS_STAGE=0 | 1 | P: off / whole block / in P phases of ceil(W / P) agents (a P-th of the LDS)
-    if (const char* os = getenv("MSC_OBS_STAGE")) c.obs_stage = c.obs_stage ? (atoi(os) > 0 ? atoi(os) : 0) : 0;
-    if (c.obs_stage > c.W) c.obs_stage = c.W;
-    // step_c with the pending ring in registers (8-wave blocks, up to 256 VGPRs): C2 (4,096 envs)
-    // 152.7 -> 157.4 M agent-steps/s; at 32,768 envs the env line is unchanged and the MAPPO rollout
-    // 1.165 -> 1.188 ms per step (fewer step_c blocks fit beside the demand kernel), so only below
-    // the lane allocator's env count (profiles/r03/ab_ringreg.txt). MSC_OBS_RING_REG=0|1 forces it.
-    c.obs_ring_reg = n_envs < 16384 ? 1 : 0;
-    if (const char* orr = getenv("MSC_OBS_RING_REG")) c.obs_ring_reg = atoi(orr) != 0;
-    // phase B: one env per lane (alloc_lane_kernel) when there are enough env chains to fill the
-    // chip and the Poisson demand kernel of the next step runs beside it (it then needs the issue
-    // slots the lane kernel leaves free: C3, 32768 envs: 0.80 vs 0.86 ms/step); otherwise the
-    // group-per-env kernel, whose 8-16x more waves shorten each chain (C5, 8192 envs x 16
-    // warehouses, empirical demand: 1.08 vs 1.71 ms/step). MSC_ALLOC_IMPL=lane|group forces one.
-    c.alloc_impl = (d->demand_type == MSC_DEMAND_POISSON && n_envs >= 16384) ? 0 : 1;
-    if (const char* al = getenv("MSC_ALLOC_IMPL")) {
-      if (strcmp(al, "group") == 0) c.alloc_impl = 1;
-      else if (strcmp(al, "lane") == 0) c.alloc_impl = 0;
-    }
-    if (W > 16 || K > 8) c.alloc_impl = 1;  // the lane allocator's instantiations stop at 16 x 8
-    c.alloc_lpe = 0;
-    if (const char* lp = getenv("MSC_ALLOC_LPE")) c.alloc_lpe = atoi(lp);
-    // group kernel over empirical demand: a wave runs as many order iterations as its busiest env,
-    // and trace order counts spread widely (C5: 200-1,000 per step), so the envs are visited in
-    // descending order of this step's count (one counting-sort launch; results do not depend on
-    // the order, every env is independent). MSC_ALLOC_SORT=0|1 forces it off / on.
-    c.alloc_sort = (c.alloc_impl == 1 && d->demand_type == MSC_DEMAND_EMPIRICAL) ? 1 : 0;
-    if (const char* so = getenv("MSC_ALLOC_SORT")) c.alloc_sort = c.alloc_impl == 1 && atoi(so) != 0 ? 1 : 0;
-    int64_t maxc = order_cap;
-    if (d->demand_type == MSC_DEMAND_EMPIRICAL) {
-      maxc = 0;
-      for (int i = 0; i < c.tr_rows; i++) maxc = std::max<int64_t>(maxc, toff[i + 1] - toff[i]);
-    }
-    c.sort_shift = 0;
-    while ((maxc >> c.sort_shift) >= SORT_BUCKETS) c.sort_shift++;
-    // few envs (BASELINE configs[1]: 4,096): the scan allocator (one env per wave, no
-    // data-dependent loop per order) at <= 8 warehouses and <= 6 SKUs. It also runs 9-16 warehouses
-    // (MSC_ALLOC_IMPL=scan) but loses there: at C5 (16 x 256, 8,192 envs, ~2.5 orders per region, so
-    // about one order per batch) 1.78 against 0.89 ms per step for the group kernel
-    // (profiles/r04/ab_c5_scan.txt). An explicit MSC_ALLOC_IMPL=group keeps the group kernel.
-    const char* al_env = getenv("MSC_ALLOC_IMPL");
-    if (c.alloc_impl == 1 && !al_env && W <= 8 && alloc_scan_supported(W, K)) c.alloc_impl = 2;
-    if (al_env && strcmp(al_env, "scan") == 0) c.alloc_impl = alloc_scan_supported(W, K) ? 2 : 1;
-    c.scan_defer = 1;
-    // phase C inside the scan allocator (one env per wave: its obs, rewards and state updates from the
-    // allocation's registers; no step_c launch). MSC_FUSE_C=0 keeps the step_c kernel.
-    c.fuse_c = c.alloc_impl == 2 ? (alloc_scan_fuse_supported(W, K, RING) ? 1 : 0)
-             : c.alloc_impl == 1 ? (K <= 8 && RING <= 4 ? 1 : 0)  // the group allocator's (step_b_phase_c)
-             : 0;
-    if (const char* fc = getenv("MSC_FUSE_C")) c.fuse_c = c.fuse_c && atoi(fc) != 0 ? 1 : 0;
-    // phase A too when it has no per-env RNG work (fixed lead times; Poisson demand: the empirical
-    // sampler draws its window start in phase A). MSC_FUSE_A=0 keeps the step_a kernel.
-    c.fuse_a = c.alloc_impl == 2 && c.fuse_c && d->lead_type != MSC_LEAD_STOCHASTIC && d->demand_type == MSC_DEMAND_POISSON ? 1 : 0;
-    c.sc_tab = 1;
-    c.sc_form = 5;
-    if (const char* sf = getenv("MSC_STEP_C_FORM")) c.sc_form = atoi(sf) == 4 ? 4 : 5;
-    // alloc_lane's waves run above the parser of the next step's demand kernel for the first 12/16
-    // of their orders, then below it: the pipelined C3 step is demand-bound with the allocation at
-    // full priority (0.755 ms demand beside 0.64 ms of step kernels) and chain-bound below it (0.61
-    // beside 0.86); 12/16 balanced them (341 -> 349 M agent-steps/s, profiles/r06/ab_alloc_prio.txt), and
-    // 14/16 does with the shorter generator draw (361 -> 368 M, profiles/gen_draw/ab_alloc_prio.txt)
-    c.al_psplit = 14;
-    if (const char* ps = getenv("MSC_AL_PRIO_SPLIT")) c.al_psplit = atoi(ps) >= 1 && atoi(ps) <= 16 ? atoi(ps) : 14;
-    if (const char* st = getenv("MSC_SC_TAB")) c.sc_tab = atoi(st) != 0 ? 1 : 0;
-    c.sb_gw = 0;
-    if (const char* g = getenv("MSC_SB_GW")) {
-      const int v = atoi(g);
-      c.sb_gw = (v == 4 || v == 8 || v == 16 || v == 32) ? v : 0;
-    }
-    if (const char* fa = getenv("MSC_FUSE_A")) c.fuse_a = c.fuse_a && atoi(fa) != 0 ? 1 : 0;
-    {
-      // step_b's block tables ({of, ov} rows [2][R][W] f64 + closest [R] i32) in LDS: when small
-      // (16 KB, room for the blocks of the pipelined demand kernel beside the step), or, with
-      // empirical demand (no demand kernel beside the step), when the step_b blocks one CU holds at
-      // this env count fit its 160 KB with them (C5, 8,192 envs x 16 warehouses: one 8-wave block per
-      // CU, 32 KB of record windows + 66.5 KB of tables); otherwise each region change reads its cost
-      // row from L2, and its wait also drains the record windows' LDS-DMA and the stores in flight
-      int ncu = 256;
-      if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || ncu < 1) ncu = 256;
-      int gw = W <= 2 ? 2 : W <= 4 ? 4 : W <= 8 ? 8 : W <= 16 ? 16 : 32;
-      if (c.sb_gw > gw) gw = c.sb_gw;  // (the validated MSC_SB_GW: the group width launch_step_k uses)
-      // (blocks of 8 waves for 16- and 32-lane groups with the tables, else 4: step_b_waves)
-      const int bw = gw >= 16 ? 8 : 4;
-      const int64_t blocks = (n_envs * gw + 64 * bw - 1) / (64 * bw), per_cu = (blocks + ncu - 1) / ncu;
-      const size_t tab = (size_t)2 * R * W * sizeof(double) + (size_t)R * sizeof(int32_t);
-      const size_t blk = (size_t)bw * 2 * 128 * 16 + tab;  // waves x 2 windows x SB_REC records + tables
-      c.sb_tab = tab <= 16 * 1024 ? 1
-               : (d->demand_type == MSC_DEMAND_EMPIRICAL && blk <= 160 * 1024 && (int64_t)blk * per_cu <= 160 * 1024) ? 1 : 0;
-      if (const char* st = getenv("MSC_SB_TAB")) c.sb_tab = atoi(st) != 0 && blk <= 160 * 1024 ? 1 : 0;
-    }
-    if (const char* sd = getenv("MSC_SCAN_DEFER")) c.scan_defer = atoi(sd) != 0 ? 1 : 0;
-    // episode-ahead Poisson demand when the envs are too few to fill the chip with per-step demand
-    // chains (MSC_EA=0|1 forces it off / on)
-    c.ea_S = 0;
-    if (d->demand_type == MSC_DEMAND_POISSON) {
-      // (automatic below 8,193 envs; at 32,768 envs it wins only in steady state -- 0.81 -> 0.72 ms
-      // per step once the generation pipeline is full, profiles/r04/ab_ea_c3.txt -- while the first
-      // episodes pay for the bulk generation, so larger handles ask for it explicitly)
-      bool want = d->episode_ahead < 0 ? n_envs <= 8192 : d->episode_ahead > 0;
-      if (const char* ea = getenv("MSC_EA")) want = atoi(ea) != 0;
-      // 16 slots: the generation runs further ahead of the step (C2 over 48 episodes: 175.5 M
-      // agent-steps/s at 12 slots, 180-183 M at 16; profiles/r03/ab_ea_slots.txt); 29 GB at 4,096 envs
-      // (the memory budget below may lower it)
-      int S = 16;
-      if (d->episode_ahead > 0 && d->episode_ahead < S) S = d->episode_ahead;
-      if (const char* es = getenv("MSC_EA_SLOTS")) S = atoi(es);
-      S = S < 2 ? 2 : (S > MSC_EA_MAX_S ? MSC_EA_MAX_S : S);
-      if (want) {
-        double lam_sum = 0.0, draws = 0.0;
-        // expected uniforms per Poisson draw: lambda + 1 for the multiplication method, a few per
-        // PTRS trial (two uniforms, acceptance > 0.5) at lambda >= 10
-        auto per_draw = [](double lam) { return lam < 10.0 ? lam + 1.0 : 8.0; };
-        for (int r = 0; r < R; r++) {
-          const double lo = d->lambda_orders[r];
-          lam_sum += lo;
-          double per_order = K;  // the SKU mask's Bernoulli draws
-          for (int s = 0; s < K; s++) per_order += d->probability_skus[r] * per_draw(d->lambda_quantity[(size_t)r * K + s]);
-          draws += per_draw(lo) + lo * per_order;
-        }
-        const double m = lam_sum * d->episode_length;
-        draws *= d->episode_length;
-        const double cap_d = ceil(m + 12.0 * sqrt(m + 1.0) + 64.0);
-        // slot record indices are int32 in the kernels and stream positions uint32: an episode whose
-        // records or draws (with a 12-sigma margin) do not fit keeps per-step demand
-        if (cap_d * nv <= (double)INT32_MAX && draws + 12.0 * sqrt(draws + 1.0) < 4294967295.0) {
-          c.ea_S = S;
-          c.ea_cap = (int64_t)cap_d;
-        }
-      }
-    }
-  }
-
-  TablePack tp;
-  std::vector<int32_t> zeros_wk(WK, 0);
-  std::vector<float> zeros_f(c.F > 0 ? c.F : 1, 0.0f), ones_f(c.F > 0 ? c.F : 1, 1.0f);
-  const size_t o_act = tp.add(d->action_param, sizeof(double) * K);
-  const size_t o_init = tp.add(d->init_values ? d->init_values : zeros_wk.data(), sizeof(int32_t) * WK);
-  const size_t o_hold = tp.add(hold.data(), sizeof(double) * K);
-  const size_t o_pen = tp.add(pen.data(), sizeof(double) * K);
-  const size_t o_skw = tp.add(d->sku_weights, sizeof(double) * K);
-  const size_t o_ofT = tp.add(ofT.data(), sizeof(double) * ofT.size());
-  const size_t o_ovT = tp.add(ovT.data(), sizeof(double) * ovT.size());
-  const size_t o_inF = tp.add(d->inbound_fixed, sizeof(double) * WK);
-  const size_t o_inV = tp.add(d->inbound_variable, sizeof(double) * WK);
-  const size_t o_elo = tp.add(enlam_o.data(), sizeof(double) * R);
-  const size_t o_ps = tp.add(p_sku.data(), sizeof(double) * R);
-  const size_t o_pk = tp.add(p_skip.data(), sizeof(double) * R);
-  const size_t o_elq = tp.add(enlam_q.data(), sizeof(double) * enlam_q.size());
-  const size_t o_pto = tp.add(ptrs_o.data(), sizeof(PtrsConst) * ptrs_o.size());
-  const size_t o_ptq = tp.add(ptrs_q.data(), sizeof(PtrsConst) * ptrs_q.size());
-  const size_t o_elt = tp.add(d->expected_lead_times, sizeof(int32_t) * WK);
-  const size_t o_md = tp.add(d->lead_type == MSC_LEAD_STOCHASTIC ? d->max_deviation : zeros_wk.data(),
-                             sizeof(int32_t) * (d->lead_type == MSC_LEAD_STOCHASTIC && d->max_dev_per_sku ? K : 1));
-  const size_t o_hm = tp.add(home_mask.data(), sizeof(uint32_t) * R);
-  const size_t o_cl = tp.add(closest.data(), sizeof(int32_t) * R);
-  const size_t o_ho = tp.add(home_of.data(), sizeof(int32_t) * W);
-  const size_t o_mean = tp.add(c.norm == MSC_OBS_MEANSTD ? d->obs_mean : zeros_f.data(), sizeof(float) * zeros_f.size());
-  const size_t o_std = tp.add(c.norm == MSC_OBS_MEANSTD ? d->obs_std : ones_f.data(), sizeof(float) * ones_f.size());
-  size_t o_toff = 0, o_trec = 0;
-  if (d->demand_type == MSC_DEMAND_EMPIRICAL) {
-    o_toff = tp.add(toff.data(), sizeof(int64_t) * toff.size());
-    o_trec = tp.add(trec.data(), sizeof(uint4) * trec.size());
-  }
+  const EnvKnobs knobs = read_env_knobs();
+  int ncu = 0;
+  if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) ncu = 0;
+  EnvPlan p;
+  if (const int rc = plan_env(d, n_envs, ncu, knobs, p)) return set_err(rc, "%s", p.err);
+  EnvConst& c = p.c;
+  const int64_t E = n_envs;
+  const int nv = p.nv;
 
   HIP_TRY(hipSetDevice(device));
   msc_env* env = new msc_env();
   env->device = device;
   auto fail = [&](int rc) {
-    if (env->tables) (void)hipFree(env->tables);
-    if (env->arena) (void)hipFree(env->arena);
-    if (env->scratch) (void)hipFree(env->scratch);
-    if (env->dev) (void)hipFree(env->dev);
-    if (env->ea_mem) (void)hipFree(env->ea_mem);
-    delete env;
+    env_release(env);
     return rc;
   };
+  Packer tp(16);
+  table_layout(d, p, tp);
   if (hipMalloc(&env->tables, tp.host.size()) != hipSuccess) return fail(set_err(-2, "hipMalloc(tables) failed"));
   if (hipMemcpy(env->tables, tp.host.data(), tp.host.size(), hipMemcpyHostToDevice) != hipSuccess)
     return fail(set_err(-2, "copy tables failed"));
-  char* tb = static_cast<char*>(env->tables);
-  c.act_param = (const double*)(tb + o_act);
-  c.init_vals = (const int32_t*)(tb + o_init);
-  c.hold = (const double*)(tb + o_hold);
-  c.pen = (const double*)(tb + o_pen);
-  c.skw = (const double*)(tb + o_skw);
-  c.ofT = (const double*)(tb + o_ofT);
-  c.ovT = (const double*)(tb + o_ovT);
-  c.inF = (const double*)(tb + o_inF);
-  c.inV = (const double*)(tb + o_inV);
-  c.enlam_o = (const double*)(tb + o_elo);
-  c.p_sku = (const double*)(tb + o_ps);
-  c.p_skip = (const double*)(tb + o_pk);
-  c.enlam_q = (const double*)(tb + o_elq);
-  c.ptrs_o = (const double*)(tb + o_pto);
-  c.ptrs_q = (const double*)(tb + o_ptq);
-  c.elt = (const int32_t*)(tb + o_elt);
-  c.maxdev = (const int32_t*)(tb + o_md);
-  c.home_mask = (const uint32_t*)(tb + o_hm);
-  c.closest = (const int32_t*)(tb + o_cl);
-  c.home_of = (const int32_t*)(tb + o_ho);
-  c.obs_mean = (const float*)(tb + o_mean);
-  c.obs_std = (const float*)(tb + o_std);
-  if (d->demand_type == MSC_DEMAND_EMPIRICAL) {
-    c.tr_off = (const int64_t*)(tb + o_toff);
-    c.tr_rec = (const uint4*)(tb + o_trec);
-  }
+  tp.resolve(env->tables);
 
-  // ---- persistent state arena (SoA, env fastest) -----------------------------------------
-  const int64_t E = n_envs;
-  const bool stoch = d->lead_type == MSC_LEAD_STOCHASTIC;
-  size_t off = 0;
-  auto slot = [&](size_t bytes) {
-    size_t o = off;
-    off = (off + bytes + 255) & ~size_t(255);
-    return o;
-  };
-  const size_t a_inv = slot(sizeof(int32_t) * WK * E);
-  const size_t a_rq = slot(sizeof(int32_t) * (size_t)WK * RING * E);
-  const size_t a_rl = slot(stoch ? (size_t)WK * RING * E : 1);
-  const size_t a_hist = slot(sizeof(int32_t) * (size_t)MSC_HISTORY * WK * E);
-  const size_t a_inc = slot(sizeof(int32_t) * WK * E);
-  const size_t a_fc = slot(sizeof(float) * WK * E);
-  const size_t a_rng = slot(sizeof(uint64_t) * 8 * E);
-  const size_t a_rbuf = slot(sizeof(uint32_t) * 4 * E);
-  const size_t a_rpre = slot(sizeof(uint64_t) * 4 * E);
-  const size_t a_bpre = slot(sizeof(uint32_t) * 2 * E);
-  const size_t a_t = slot(sizeof(int32_t) * E);
-  const size_t a_cnt = slot(sizeof(int32_t) * E);
-  const size_t a_orig = slot(sizeof(uint32_t) * E);
-  const size_t a_root = slot(sizeof(uint32_t) * E);
-  const size_t a_emp = slot(sizeof(int32_t) * E);
-  const size_t a_perm = slot(sizeof(int32_t) * E);
-  const size_t a_err = slot(sizeof(uint32_t) * 4);
-  const size_t a_sht = slot(sizeof(int32_t) * WK * E);
-  const size_t a_shh = slot(sizeof(int32_t) * WK * E);
-  const size_t a_pen = slot(sizeof(double) * W * E);
-  const size_t a_out = slot(sizeof(double) * W * E);
-  const size_t a_inb = slot(sizeof(double) * W * E);
-  env->arena_bytes = off;
-  if (hipMalloc(&env->arena, off) != hipSuccess) return fail(set_err(-2, "hipMalloc(state arena, %zu B) failed", off));
-  if (hipMemset(env->arena, 0, off) != hipSuccess) return fail(set_err(-2, "memset arena failed"));
-  char* ab = static_cast<char*>(env->arena);
   EnvState s{};
-  s.inv = (int32_t*)(ab + a_inv);
-  s.ring_q = (int32_t*)(ab + a_rq);
-  s.ring_l = (uint8_t*)(ab + a_rl);
-  s.hist = (int32_t*)(ab + a_hist);
-  s.inc = (int32_t*)(ab + a_inc);
-  s.fc = (float*)(ab + a_fc);
-  s.rng = (uint64_t*)(ab + a_rng);
-  s.rbuf = (uint32_t*)(ab + a_rbuf);
-  s.rng_pre = (uint64_t*)(ab + a_rpre);
-  s.rbuf_pre = (uint32_t*)(ab + a_bpre);
-  s.t = (int32_t*)(ab + a_t);
-  s.counter = (int32_t*)(ab + a_cnt);
-  s.orig_root = (uint32_t*)(ab + a_orig);
-  s.root = (uint32_t*)(ab + a_root);
-  s.emp_start = (int32_t*)(ab + a_emp);
-  s.perm = (int32_t*)(ab + a_perm);
-  s.err = (uint32_t*)(ab + a_err);
-  s.sc_sht = (int32_t*)(ab + a_sht);
-  s.sc_shh = (int32_t*)(ab + a_shh);
-  s.sc_pen = (double*)(ab + a_pen);
-  s.sc_out = (double*)(ab + a_out);
-  s.sc_inb = (double*)(ab + a_inb);
-  EnvState s2 = s;
-  if (d->demand_type == MSC_DEMAND_POISSON) {
-    const size_t rec_bytes = sizeof(uint4) * (size_t)nv * order_cap * E;
-    env->order_bytes = (rec_bytes + sizeof(int32_t) * E + 255) & ~size_t(255);
+  Packer ap(256);
+  arena_layout(c, s, ap);
+  env->arena_bytes = ap.padded();
+  if (hipMalloc(&env->arena, env->arena_bytes) != hipSuccess)
+    return fail(set_err(-2, "hipMalloc(state arena, %zu B) failed", env->arena_bytes));
+  if (hipMemset(env->arena, 0, env->arena_bytes) != hipSuccess) return fail(set_err(-2, "memset arena failed"));
+  ap.resolve(env->arena);
+  if (c.demand_type == MSC_DEMAND_POISSON) {  // two per-step order buffers (s: the first; s2 below: the second)
+    env->order_bytes = order_buffer_bytes(c, nv);
     if (hipMalloc(&env->scratch, 2 * env->order_bytes) != hipSuccess)
       return fail(set_err(-2, "hipMalloc(order buffers, %zu B) failed", 2 * env->order_bytes));
-    for (int b = 0; b < 2; b++) {
-      char* base = (char*)env->scratch + b * env->order_bytes;
-      EnvState& sb = b ? s2 : s;
-      sb.orders = (uint4*)base;
-      sb.n_orders = (int32_t*)(base + rec_bytes);
-    }
+    s.orders = (uint4*)env->scratch;
+    s.n_orders = (int32_t*)((char*)env->scratch + order_record_bytes(c, nv));
   }
-  if (c.ea_S > 0) {
-    // episode-ahead memory budget: at most ea_mem_fraction (default 0.25, MSC_EA_MEM_FRAC) of the
-    // memory free now, so the rollout / learner allocations that follow keep the rest; the slot
-    // count shrinks to what fits, and below 2 slots EA stays off
-    const int T = c.T;
-    const size_t slot_bytes = sizeof(uint4) * (size_t)nv * c.ea_cap * E + sizeof(int32_t) * (size_t)(T + 1) * E +
-                              sizeof(uint32_t) * (size_t)T * E + sizeof(int32_t) * (size_t)E;
-    double frac = d->ea_mem_fraction > 0.0 ? d->ea_mem_fraction : 0.25;
-    if (const char* mf = getenv("MSC_EA_MEM_FRAC")) frac = atof(mf);
+  if (c.ea_S > 0) {  // the slots that fit the memory free now
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
       (void)hipGetLastError();
       free_b = 0;
     }
-    const double budget = frac * (double)free_b;
-    const int64_t fit = (int64_t)(budget / (double)(slot_bytes + 1024 /* alignment slack */));
-    if (fit < c.ea_S) c.ea_S = fit < 2 ? 0 : (int)fit;
-    env->ea_budget = (int64_t)budget;
+    const EaFit fit = ea_fit_slots(c, nv, p.ea_frac, (int64_t)free_b);
+    c.ea_S = fit.slots;
+    env->ea_budget = fit.budget;
   }
   if (c.ea_S > 0) {  // episode-ahead buffers; without the memory EA stays off
-    const int S = c.ea_S, T = c.T;
-    const size_t rec = sizeof(uint4) * (size_t)nv * c.ea_cap * S * E;
-    const size_t offb = sizeof(int32_t) * (size_t)S * (T + 1) * E, posb = sizeof(uint32_t) * (size_t)S * T * E;
-    const size_t cntb = sizeof(int32_t) * (size_t)S * E;
-    auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
-    env->ea_bytes = (int64_t)(al(rec) + al(offb) + al(posb) + al(cntb));
-    if (hipMalloc(&env->ea_mem, al(rec) + al(offb) + al(posb) + al(cntb)) == hipSuccess) {
-      char* b = (char*)env->ea_mem;
-      s.ea_rec = s2.ea_rec = (uint4*)b;
-      s.ea_off = s2.ea_off = (int32_t*)(b + al(rec));
-      s.ea_pos = s2.ea_pos = (uint32_t*)(b + al(rec) + al(offb));
-      s.ea_cnt = s2.ea_cnt = (int32_t*)(b + al(rec) + al(offb) + al(posb));
+    Packer ep(256);
+    ea_layout(c, nv, s, ep);
+    if (hipMalloc(&env->ea_mem, ep.padded()) == hipSuccess) {
+      ep.resolve(env->ea_mem);
+      env->ea_bytes = (int64_t)ep.padded();
       env->ea_enabled = true;
-      env->obs_stage_pe = c.obs_stage;
-      env->chain_prio_pe = c.chain_prio;
-      // refill batch: a batch freed by episodes n-B+1 .. n is needed S-B episodes later. A generation
-      // chunk's duration is one lane's parse chain whatever the slots per launch, so the slots per
-      // launch set the generation rate: at 4,096 envs 4 per launch (16,384 lanes) could not keep up
-      // with the step (C2 sustained 173 M agent-steps/s over 96 episodes), 8 per launch can (207 M,
-      // profiles/r05/ab_ea_batch.txt); at 32,768 envs a single slot per launch already fills the chip
-      int B = E <= 8192 ? S / 2 : S / 4;
-      B = B > 1 ? B : 1;
-      if (const char* eb = getenv("MSC_EA_BATCH")) B = atoi(eb);
-      env->ea_batch = B < 1 ? 1 : (B > S - 1 ? S - 1 : B);
-      // step_c's observation staging (up to 80 KB of LDS per block) stalls behind a generation
-      // chunk's pending blocks for the chunk's whole run (measured: 5.5 ms step_c launches right
-      // after a chunk starts, none without staging): off with EA unless MSC_OBS_STAGE=1
-      const char* os = getenv("MSC_OBS_STAGE");
-      if (!(os && atoi(os) != 0)) c.obs_stage = 0;
-      // the generation waves (parser 2, generators 1) are background work: the whole step chain
-      // runs above them (the allocation kernels are at 3 already; MSC_CHAIN_PRIO=0 leaves step_a /
-      // step_c at 0)
-      const char* cp = getenv("MSC_CHAIN_PRIO");
-      c.chain_prio = (cp && atoi(cp) == 0) ? 0 : 1;
-      // chunk A/B at C2 (scripts/gpu_ab_eachunk.sh, steps per launch -> M agent-steps/s): 5 -> 149.6,
-      // 10 -> 152.9, 20 -> 157.8, 34 -> 165.3, 50 -> 170.1, 100 -> 171.4 (fewer launch ramps and
-      // tails beside the step kernels); 50 keeps the work a synchronize may wait for at half an episode
-      // at 32,768 envs whole-episode launches: 0.72 ms per step against 0.78 with 50-step chunks
-      // (profiles/r04/ab_ea_c3.txt)
-      int ch = E > 8192 ? T : 50;
-      if (const char* ec = getenv("MSC_EA_CHUNK")) ch = atoi(ec);
-      env->ea_chunk = ch < 1 ? 1 : ch;
     } else {
       (void)hipGetLastError();
       env->ea_mem = nullptr;
-      env->ea_bytes = 0;
       c.ea_S = 0;
     }
   }
+  EnvState s2 = s;
+  if (s.orders) {
+    s2.orders = (uint4*)((char*)s.orders + env->order_bytes);
+    s2.n_orders = (int32_t*)((char*)s.n_orders + env->order_bytes);
+  }
+  // the per-step and the EA values of step_c's staging and the chain priority, both fixed here
+  // (msc_env_set_episode_ahead swaps between them); a handle with EA starts with the EA pair
+  const EaRun run = ea_run_settings(c, knobs);
+  env->obs_stage_pe = c.obs_stage;
+  env->chain_prio_pe = c.chain_prio;
+  c.obs_stage = env->obs_stage_ea = run.obs_stage;
+  c.chain_prio = env->chain_prio_ea = run.chain_prio;
+  env->ea_batch = run.batch;
+  env->ea_chunk = run.chunk;
   // root seeds: explicit, or SeedSequence([base_seed, worker_index, env_index])
   std::vector<uint32_t> roots(E);
   std::vector<int32_t> minus1(E, -1);
@@ -791,10 +363,6 @@ int msc_env_create(const msc_env_desc* d, int device, int64_t n_envs, uint32_t b
       hipMemcpy(s.root, roots.data(), sizeof(uint32_t) * E, hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(s.emp_start, minus1.data(), sizeof(int32_t) * E, hipMemcpyHostToDevice) != hipSuccess)
     return fail(set_err(-2, "seed upload failed"));
-  // The step kernel of step t runs concurrently with the demand kernel of step t+1 (pipelining):
-  // stage the outbound cost table in LDS only when two blocks of each still fit one CU's LDS.
-  // Otherwise the step kernel's blocks wait for the demand kernel's and nothing overlaps
-  // (measured: 3.4 -> 2.2 ms per step at 8x64x5 with the table in global memory).
   env->c = c;
   env->s = s;
   {
@@ -803,21 +371,13 @@ int msc_env_create(const msc_env_desc* d, int device, int64_t n_envs, uint32_t b
         hipMemcpy(env->dev, hd, 2 * sizeof(DevEnv), hipMemcpyHostToDevice) != hipSuccess)
       return fail(set_err(-2, "device descriptor upload failed"));
   }
-  {
-    const char* pl = getenv("MSC_PIPELINE");
-    env->pipeline = !(pl && strcmp(pl, "0") == 0) && d->demand_type == MSC_DEMAND_POISSON;
-  }
+  env->pipeline = p.pipeline;
+  env->ev_elide = p.ev_elide;
   if (hipStreamCreateWithFlags(&env->side, hipStreamNonBlocking) != hipSuccess)
     return fail(set_err(-2, "side stream creation failed"));
-  // the pipelining events only order work between two streams of this device (no host waits on
-  // them), so their records skip the system-scope fence: ~2 us less per record (tools/ev_gap.hip),
-  // C2 224 -> 227 M, C3 +0.3 % (profiles/r06/ab_ev_nofence.txt). MSC_EV_SCOPE=system restores it,
-  // =device records them with a device-scope release (A/B)
-  unsigned evf = hipEventDisableTiming | hipEventDisableSystemFence;
-  if (const char* es = getenv("MSC_EV_SCOPE"))
-    evf = hipEventDisableTiming | (strcmp(es, "device") == 0   ? hipEventReleaseToDevice
-                                   : strcmp(es, "system") == 0 ? 0u
-                                                               : hipEventDisableSystemFence);
+  const unsigned evf = hipEventDisableTiming | (p.ev_scope == EnvKnobs::EvScope::device   ? hipEventReleaseToDevice
+                                                : p.ev_scope == EnvKnobs::EvScope::system ? 0u
+                                                                                          : hipEventDisableSystemFence);
   for (int b = 0; b < 2; b++)
     if (hipEventCreateWithFlags(&env->ev_dem[b], evf) != hipSuccess ||
         hipEventCreateWithFlags(&env->ev_step[b], evf) != hipSuccess)
@@ -831,12 +391,10 @@ int msc_env_create(const msc_env_desc* d, int device, int64_t n_envs, uint32_t b
   }
   (void)hipEventRecord(env->ev_reset, env->side);
   env->side_saw_reset = true;
-  if (const char* el = getenv("MSC_EV_ELIDE")) env->ev_elide = strcmp(el, "0") != 0;
   if (env->ea_enabled) {
-    // MSC_EA_PRIO=low|high: queue priority of the generation stream (A/B; default: normal)
-    int ea_prio = 0, lo = 0, hi = 0;
+    int lo = 0, hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-    if (const char* ep = getenv("MSC_EA_PRIO")) ea_prio = strcmp(ep, "low") == 0 ? lo : strcmp(ep, "high") == 0 ? hi : 0;
+    const int ea_prio = p.ea_prio == EnvKnobs::EaPrio::low ? lo : p.ea_prio == EnvKnobs::EaPrio::high ? hi : 0;
     if (hipStreamCreateWithPriority(&env->ea_stream, hipStreamNonBlocking, ea_prio) != hipSuccess)
       return fail(set_err(-2, "EA stream creation failed"));
     for (int j = 0; j < MSC_EA_MAX_S; j++)
@@ -859,26 +417,26 @@ void msc_env_destroy(msc_env* env) {
   if (!env) return;
   (void)hipSetDevice(env->device);
   (void)hipDeviceSynchronize();
-  if (env->tables) (void)hipFree(env->tables);
-  if (env->arena) (void)hipFree(env->arena);
-  if (env->scratch) (void)hipFree(env->scratch);
-  if (env->dev) (void)hipFree(env->dev);
-  for (int b = 0; b < 2; b++) {
-    if (env->ev_dem[b]) (void)hipEventDestroy(env->ev_dem[b]);
-    if (env->ev_step[b]) (void)hipEventDestroy(env->ev_step[b]);
-  }
-  if (env->ev_reset) (void)hipEventDestroy(env->ev_reset);
-  for (int j = 0; j < MSC_EA_MAX_S; j++) {
-    if (env->ev_gen[j]) (void)hipEventDestroy(env->ev_gen[j]);
-    if (env->ev_cons[j]) (void)hipEventDestroy(env->ev_cons[j]);
-  }
-  if (env->ev_snap) (void)hipEventDestroy(env->ev_snap);
-  if (env->ev_chunk) (void)hipEventDestroy(env->ev_chunk);
-  if (env->ea_mem) (void)hipFree(env->ea_mem);
-  timing_free(env);
-  if (env->side) (void)hipStreamDestroy(env->side);
-  if (env->ea_stream) (void)hipStreamDestroy(env->ea_stream);
-  delete env;
+  env_release(env);
+}
+
+int msc_env_plan(const msc_env_desc* d, int64_t n_envs, int32_t n_cus, int64_t free_bytes, int32_t* out, int32_t n) {
+  if (!d || (!out && n > 0)) return set_err(-1, "null argument");
+  const EnvKnobs knobs = read_env_knobs();
+  EnvPlan p;
+  if (const int rc = plan_env(d, n_envs, n_cus, knobs, p)) return set_err(rc, "%s", p.err);
+  EnvConst& c = p.c;
+  if (c.ea_S > 0 && free_bytes >= 0) c.ea_S = ea_fit_slots(c, p.nv, p.ea_frac, free_bytes).slots;
+  const EaRun run = ea_run_settings(c, knobs);
+  c.obs_stage = run.obs_stage;
+  EnvState s{};
+  Packer ap(256);
+  arena_layout(c, s, ap);
+  int32_t v[PLAN_N];
+  plan_values(c, run, p.pipeline, ap.padded(), order_buffer_bytes(c, p.nv), v);
+  const int m = n < PLAN_N ? n : PLAN_N;
+  for (int i = 0; i < m; i++) out[i] = v[i];
+  return m;
 }
 
 int msc_env_ea_memory(const msc_env* env, int64_t* budget_bytes, int64_t* allocated_bytes) {
@@ -904,12 +462,8 @@ int msc_env_dims(const msc_env* env, int64_t* n_envs, int32_t* n_agents, int32_t
 
 int msc_env_kernel_choice(const msc_env* env, int32_t* out, int32_t n) {
   if (!env || (!out && n > 0)) return set_err(-1, "null argument");
-  const EnvConst& c = env->c;
-  const int W = c.W;
-  int gw = W <= 2 ? 2 : W <= 4 ? 4 : W <= 8 ? 8 : W <= 16 ? 16 : 32;
-  if (c.sb_gw > gw) gw = c.sb_gw;
-  const int32_t v[9] = {c.alloc_impl, c.alloc_sort, c.fuse_a, c.fuse_c, c.sb_tab, c.alloc_impl == 1 ? gw : 0,
-                        env->ea_enabled ? c.ea_S : 0, c.demand_impl, c.demand_uni};
+  int32_t v[PLAN_N];  // the first nine of msc_env_plan's list (c.ea_S is 0 unless the EA buffers exist)
+  plan_values(env->c, EaRun{env->ea_batch, env->ea_chunk, 0, 0}, env->pipeline, env->arena_bytes, env->order_bytes, v);
   const int m = n < 9 ? n : 9;
   for (int i = 0; i < m; i++) out[i] = v[i];
   return m;
@@ -1067,12 +621,8 @@ int msc_env_set_episode_ahead(msc_env* env, int32_t enabled) {
   env->ea_paused = pause;
   // the per-step path's step_c staging and chain priority (EA runs without staging, chain above the
   // generation waves); patched into both device descriptors
-  const int32_t stage = pause ? env->obs_stage_pe : 0;
-  const int32_t prio = pause ? env->chain_prio_pe : 1;
-  const char* os = getenv("MSC_OBS_STAGE");
-  const char* cp = getenv("MSC_CHAIN_PRIO");
-  env->c.obs_stage = (!pause && os && atoi(os) != 0) ? env->obs_stage_pe : stage;
-  env->c.chain_prio = (!pause && cp && atoi(cp) == 0) ? 0 : prio;
+  env->c.obs_stage = pause ? env->obs_stage_pe : env->obs_stage_ea;
+  env->c.chain_prio = pause ? env->chain_prio_pe : env->chain_prio_ea;
   for (int b = 0; b < 2; b++) {
     HIP_TRY(hipMemcpy(&env->dev[b].c.obs_stage, &env->c.obs_stage, sizeof(int32_t), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(&env->dev[b].c.chain_prio, &env->c.chain_prio, sizeof(int32_t), hipMemcpyHostToDevice));

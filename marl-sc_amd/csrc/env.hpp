@@ -200,8 +200,6 @@ hipError_t launch_demand_ea(const EnvConst& c, const DevEnv* d, const EaLaunch& 
 hipError_t launch_ea_materialize(const EnvConst& c, const DevEnv* d, int slot, int t_done, hipStream_t st);
 // alloc_scan.hip
 hipError_t launch_alloc_scan(const EnvConst& c, const DevEnv* d, const StepIO& io, hipStream_t st);
-bool alloc_scan_fuse_supported(int W, int K, int RING);
-bool alloc_scan_supported(int W, int K);
 constexpr int SORT_BUCKETS = 1024;
 // alloc_kernels.hip
 hipError_t launch_alloc_lane(const EnvConst& c, const DevEnv* d, const StepIO& io, hipStream_t st);
@@ -215,7 +213,6 @@ bool demand_v3_supported(const EnvConst& c);
 hipError_t launch_demand_v3(const EnvConst& c, const DevEnv* d, hipStream_t st, const EaLaunch* ea);
 hipError_t launch_gen_draws(int G, const uint64_t* state, const uint64_t* inc, int64_t n, uint64_t* out,
                             uint64_t* state_out, hipStream_t st);
-int order_record_vec4(int K);
 // policy.hip: the baseline policies' action kernel (msc_policy_act). Device pointers; tables by candidate
 struct PolicyDev {
   int32_t kind, n_cand, h_max;

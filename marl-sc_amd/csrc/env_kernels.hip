@@ -15,6 +15,7 @@
 #include <math.h>
 
 #include "env.hpp"
+#include "env_plan.hpp"
 #include "kcommon.hpp"
 #include "rng.hpp"
 #include "demand_common.hpp"
@@ -1529,8 +1530,6 @@ MSC_EK_DECL(w1)
 MSC_EK_DECL(w2)
 #undef MSC_EK_DECL
 
-int order_record_vec4(int K) { return (1 + K + 7) / 8; }
-
 void launch_alloc_sort(const DevEnv* d, const StepIO& io, hipStream_t st) {
   hipLaunchKernelGGL(alloc_sort_kernel, dim3(1), dim3(1024), 0, st, d, io);
 }
@@ -1624,8 +1623,7 @@ static hipError_t launch_step_k(const EnvConst& c, const DevEnv* d, const StepIO
   }
   using KFn = void (*)(const DevEnv*, StepIO);
   // three phase kernels, group-per-env allocation
-  int GW = c.W <= 2 ? 2 : c.W <= 4 ? 4 : c.W <= 8 ? 8 : c.W <= 16 ? 16 : 32;
-  if (c.sb_gw > GW) GW = c.sb_gw;  // (A/B: wider lane groups, fewer envs per wave)
+  const int GW = step_b_group_width(c.W, c.sb_gw);
   const bool dbg = io.has_info != 0;  // collect_step_info: the instrumented instantiations
   // step_a / step_c: one wave per warehouse, or (> 16 warehouses, > 8 SKUs) LW waves looping
   constexpr int LW = step_loop_waves(K);

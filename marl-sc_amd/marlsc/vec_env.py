@@ -32,6 +32,32 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+# msc_env_plan's list (include/marlsc.h); msc_env_kernel_choice reports the first nine
+PLAN_KEYS = ("alloc", "alloc_sort", "fuse_a", "fuse_c", "group_tables_lds", "group_width", "ea_slots",
+             "demand_impl", "demand_uni",
+             "obs_stage", "obs_ring_reg", "alloc_lpe", "sort_shift", "scan_defer", "sc_tab", "sc_form", "al_psplit",
+             "demand_ptrs", "order_cap", "ring", "ea_cap", "ea_batch", "ea_chunk", "pipeline",
+             "arena_bytes", "order_bytes")
+
+
+def plan(spec: EnvSpec, n_envs: int, *, n_cus: int = 256, free_bytes: int = -1,
+         episode_ahead: Optional[int] = None, ea_mem_fraction: float = 0.0) -> Dict[str, int]:
+    """What msc_env_create would choose for `spec` at n_envs under the current MSC_* knobs
+    (msc_env_plan): host code only, no GPU is touched. free_bytes < 0 leaves the episode-ahead memory
+    fit out. The two byte counts are returned in bytes."""
+    desc = spec.to_desc()
+    desc.episode_ahead = -1 if episode_ahead is None else int(episode_ahead)
+    desc.ea_mem_fraction = float(ea_mem_fraction)
+    buf = (C.c_int32 * len(PLAN_KEYS))()
+    n = abi.lib().msc_env_plan(C.byref(desc), int(n_envs), int(n_cus), int(free_bytes), buf, len(PLAN_KEYS))
+    if n < 0:
+        abi.check(n)
+    out = {k: int(buf[i]) for i, k in enumerate(PLAN_KEYS[:n])}
+    for k in ("arena_bytes", "order_bytes"):
+        out[k] *= 256
+    return out
+
+
 class VecInventoryEnv:
     def __init__(self, env_config: Any, n_envs: int, *, env_meta: Optional[Dict[str, Any]] = None,
                  device: int = 0, base_seed: Optional[int] = None, worker_index: int = 0,
@@ -194,8 +220,7 @@ class VecInventoryEnv:
 
     def kernel_choice(self) -> Dict[str, int]:
         """The kernels this handle runs (msc_env_kernel_choice), chosen at create time by shape."""
-        keys = ("alloc", "alloc_sort", "fuse_a", "fuse_c", "group_tables_lds", "group_width", "ea_slots",
-                "demand_impl", "demand_uni")
+        keys = PLAN_KEYS[:9]
         buf = (C.c_int32 * len(keys))()
         n = abi.lib().msc_env_kernel_choice(self._h, buf, len(keys))
         if n < 0:

@@ -896,3 +896,37 @@ def test_scan_allocator_wide_step_info_vs_group(monkeypatch, W, K):
                 np.testing.assert_allclose(sc[k], g[k], rtol=0, atol=1e-9, err_msg=f"{k} t={t}")
             else:
                 np.testing.assert_array_equal(sc[k], g[k], err_msg=f"{k} t={t}")
+
+
+def _plan_shape(name):
+    if name == "repo_3wh5sku":
+        return spec_of(*load(name)), 300
+    if name == "trace":  # empirical demand: the group allocator over envs sorted by order count
+        from marlsc.synthetic import make_synthetic_trace
+        cfg = make_synthetic_env_config(3, 5, 7, episode_length=6)  # 7 SKUs: no scan allocator
+        cfg["components"]["demand_sampler"] = {"type": "empirical", "params": None}
+        meta = {"include_warehouse_id": True, "demand_trace": make_synthetic_trace(5, 7, 25, orders_per_step=(2, 12), seed=3)}
+        return EnvSpec.from_config(cfg, meta), 300
+    spec = EnvSpec.from_config(make_synthetic_env_config(2, 4, 2), {"include_warehouse_id": True})
+    return spec, int(name[3:])  # "c1_<envs>": scan allocator with episode-ahead demand / lane allocator
+
+
+@pytest.mark.parametrize("name", ["c1_128", "c1_16384", "repo_3wh5sku", "trace"])
+def test_created_handle_runs_what_the_plan_says(monkeypatch, name):
+    # msc_env_plan (the create-time choice as pure host code, pinned on the CPU by test_env_plan_host.py)
+    # against what a handle created for the same descriptor reports, on this device's CU count; the
+    # checkpoint size is the header plus the plan's arena and one order buffer
+    from marlsc import abi
+    from marlsc.vec_env import plan
+    for k in ("MSC_ALLOC_IMPL", "MSC_ALLOC_LPE", "MSC_ALLOC_SORT", "MSC_OBS_STAGE", "MSC_OBS_RING_REG", "MSC_FUSE_C",
+              "MSC_FUSE_A", "MSC_EA", "MSC_SB_GW", "MSC_SB_TAB", "MSC_DEMAND_IMPL", "MSC_DEMAND_UNI", "MSC_EA_SLOTS"):
+        monkeypatch.delenv(k, raising=False)
+    spec, E = _plan_shape(name)
+    want = plan(spec, E, n_cus=torch.cuda.get_device_properties(0).multi_processor_count, free_bytes=-1)
+    env = _vec(spec, E)
+    kc = env.kernel_choice()
+    assert kc == {k: want[k] for k in kc}, (kc, want)
+    assert kc["alloc"] == {"c1_128": 2, "c1_16384": 0, "repo_3wh5sku": 2, "trace": 1}[name]
+    assert (kc["ea_slots"] > 0) == (name in ("c1_128", "repo_3wh5sku")) and kc["alloc_sort"] == (name == "trace")
+    assert abi.lib().msc_env_state_bytes(env._h) == 16 + want["arena_bytes"] + want["order_bytes"]
+    env.close()
