@@ -18,7 +18,10 @@
 //    neither store tests the capacity (an overflowing env rewrites its last record and raises the
 //    error flag, as before);
 //  * the generators' high word converted by one v_cvt_f64_u32 (laundered: the optimizer otherwise
-//    widens it into a 64-bit conversion with an add).
+//    widens it into a 64-bit conversion with an add;
+//  * a refill quota of its own (21 positions per chunk against the unit kernel's 24) and, in place of
+//    the unit kernel's top-up barrier, a lane throttle: a lane short of a chunk's worth of generated
+//    positions sits the chunk out.
 #include <hip/hip_runtime.h>
 
 #include "demand_common.hpp"
@@ -26,8 +29,28 @@
 namespace msc {
 
 #ifdef MSC_PROF
-__device__ unsigned long long g_prof_v3[8];  // [0] parser rounds, [2] parser waves
+// [0] parser rounds (wave level), [2] parser waves, [3] throttled lane-chunks, [4] generator passes
+// (wave level), [5] draws generated
+__device__ unsigned long long g_prof_v3[8];
 #endif
+
+// The generators' refill quota: positions added per lane per chunk, a function of the chunk index
+// that parser and generators both evaluate (A/B: variant builds of this translation unit). The
+// parser consumes ~18 positions per chunk at lambda 4-5; the unit kernel keeps MSC_GEN_QUOTA.
+#ifndef MSC_V3_QUOTA
+#define MSC_V3_QUOTA 21  // even chunks
+#endif
+#ifndef MSC_V3_QUOTA_ODD
+#define MSC_V3_QUOTA_ODD MSC_V3_QUOTA  // odd chunks
+#endif
+static_assert(MSC_V3_QUOTA > 0 && MSC_V3_QUOTA % 3 == 0 && MSC_V3_QUOTA_ODD > 0 && MSC_V3_QUOTA_ODD % 3 == 0,
+              "whole generator passes (G = 3)");
+// the fill target for chunk ci: the quota more, capped by the ring slots the parser's current chunk
+// (starting at rdp) cannot read
+__device__ __forceinline__ int v3_quota(int tgt, int rdp, int ci) {
+  const int q = tgt + ((ci & 1) ? MSC_V3_QUOTA_ODD : MSC_V3_QUOTA), cap = rdp + UCAP;
+  return q < cap ? q : cap;
+}
 
 template <int K, int G, bool EA>
 __global__ __launch_bounds__(BS * (1 + G)) __attribute__((amdgpu_waves_per_eu(MSC_DEM_WPE))) void demand_v3_kernel(
@@ -96,7 +119,21 @@ __global__ __launch_bounds__(BS * (1 + G)) __attribute__((amdgpu_waves_per_eu(MS
     if constexpr (G > 1) pcg_jump_coeffs(G, ih, il, mh, ml, ch, cl);
     int pg = g;
     GenLane gl = gen_lane(th, tl, ch, cl);  // (the draw: gen_uniform / gen_advance, demand_common.hpp)
+#ifdef MSC_PROF
+    unsigned long long n_pass = 0, n_draw = 0;
+#endif
     auto gen_to = [&](int target) {
+#ifdef MSC_PROF
+      // passes the wave executes: the most any of its lanes has to draw
+      int it = valid && pg < target ? (target - pg + G - 1) / G : 0;
+      n_draw += (unsigned long long)it;
+      for (int o = BS / 2; o > 0; o >>= 1) {
+        const int other = __shfl_xor(it, o, BS);
+        it = it > other ? it : other;
+      }
+      n_pass += (unsigned long long)it;
+#endif
+      if (!valid) return;
       while (pg < target) {
         const double u = gen_uniform(gl);
         const int sl = pg & (UCAP - 1);
@@ -107,21 +144,21 @@ __global__ __launch_bounds__(BS * (1 + G)) __attribute__((amdgpu_waves_per_eu(MS
       }
     };
     int tgt = UCAP;
-    if (valid) gen_to(UCAP);
+    gen_to(UCAP);
     __syncthreads();
+    // one refill and one barrier per chunk: a lane left short of a chunk's worth sits that chunk out
+    // in the parser (its throttle, below) instead of holding the block for a top-up
     for (int ci = 0;; ci++) {
       const int rdp = rdv[(ci & 1) * BS + lane];
-      tgt = unit_quota(tgt, rdp);
-      if (valid) gen_to(tgt);
+      tgt = v3_quota(tgt, rdp, ci);
+      gen_to(tgt);
       __syncthreads();
       if (!more[ci & 1]) break;
-      const int need = rdv[((ci + 1) & 1) * BS + lane] + UHS * UD;
-      if (__ballot(valid && tgt < need) != 0) {
-        tgt = tgt > need ? tgt : need;
-        if (valid) gen_to(tgt);
-        __syncthreads();
-      }
     }
+#ifdef MSC_PROF
+    if (lane == 0) atomicAdd(&g_prof_v3[4], n_pass);
+    if (n_draw) atomicAdd(&g_prof_v3[5], n_draw);
+#endif
     return;
   }
 
@@ -210,41 +247,45 @@ __global__ __launch_bounds__(BS * (1 + G)) __attribute__((amdgpu_waves_per_eu(MS
     x = 0;
   };
 #ifdef MSC_PROF
-  unsigned long long n_round = 0;
+  unsigned long long n_round = 0, n_thr = 0;
 #endif
   int ptgt = UCAP, rd_start = 0;  // the generators' fill target and the chunk's start position
+  bool ok = true;                 // the lane parses this chunk (false: throttled, its ring refills)
   for (int ci = 0;; ci++) {
-#pragma unroll 1
-    for (int hs = 0; hs < UHS; hs++) {
-      // issue this round's ring reads first, then book the unit that ended last round while they
-      // are in flight
-      const double* rp = myring + (rd & (UCAP - 1)) * BS;
-      double u[UD];
-#pragma unroll
-      for (int i = 0; i < UD; i++) u[i] = rp[i * BS];
-      if (pend) settle();
-      // Poisson unit: p_i = p_{i-1} U_i in draw order (bit-exact with numpy); U_i < 1 makes the
-      // products non-increasing, so "p_i > exp(-lambda)" holds for a leading run and its length is a
-      // plain count. Mask unit: bit i = SKU drawn <=> U_i < p <=> !(U_i > p_skip).
-      double p = prod;
-      int ncont = 0;
-      unsigned bits = 0;
-#pragma unroll
-      for (int i = 0; i < UD; i++) {
-        p = p * u[i];
-        ncont += p > thr ? 1 : 0;
-        if (i < K) bits |= u[i] > thr_m ? 0u : (1u << i);
-      }
-      const int go = ncont >= UD ? 1 : 0;  // Poisson unit still running after UD draws
-      const int cons = mf ? K : (go ? UD : ncont + 1);
-      mask = mf ? bits : mask;
-      x += ncont;  // (a mask unit's x is unused and cleared by its settle)
-      prod = p;
-      rd += live ? cons : 0;
-      pend = live & (mf | (go ^ 1));
 #ifdef MSC_PROF
-      n_round++;
+    n_round += __ballot(ok) != 0 ? UHS : 0;
+    n_thr += !ok && live ? 1 : 0;
 #endif
+    if (ok) {
+#pragma unroll 1
+      for (int hs = 0; hs < UHS; hs++) {
+        // issue this round's ring reads first, then book the unit that ended last round while they
+        // are in flight
+        const double* rp = myring + (rd & (UCAP - 1)) * BS;
+        double u[UD];
+#pragma unroll
+        for (int i = 0; i < UD; i++) u[i] = rp[i * BS];
+        if (pend) settle();
+        // Poisson unit: p_i = p_{i-1} U_i in draw order (bit-exact with numpy); U_i < 1 makes the
+        // products non-increasing, so "p_i > exp(-lambda)" holds for a leading run and its length is a
+        // plain count. Mask unit: bit i = SKU drawn <=> U_i < p <=> !(U_i > p_skip).
+        double p = prod;
+        int ncont = 0;
+        unsigned bits = 0;
+#pragma unroll
+        for (int i = 0; i < UD; i++) {
+          p = p * u[i];
+          ncont += p > thr ? 1 : 0;
+          if (i < K) bits |= u[i] > thr_m ? 0u : (1u << i);
+        }
+        const int go = ncont >= UD ? 1 : 0;  // Poisson unit still running after UD draws
+        const int cons = mf ? K : (go ? UD : ncont + 1);
+        mask = mf ? bits : mask;
+        x += ncont;  // (a mask unit's x is unused and cleared by its settle)
+        prod = p;
+        rd += live ? cons : 0;
+        pend = live & (mf | (go ^ 1));
+      }
     }
     // a lane with a booked-but-unsettled unit is still live: it settles in the next round
     const bool any = __ballot(live) != 0;
@@ -252,13 +293,18 @@ __global__ __launch_bounds__(BS * (1 + G)) __attribute__((amdgpu_waves_per_eu(MS
     if (lane == 0) more[ci & 1] = any ? 1 : 0;
     __syncthreads();
     if (!any) break;
-    // the generators' refill decision, restated: their top-up barrier (if any) is joined here
-    ptgt = unit_quota(ptgt, rd_start);
-    const int need = rd + UHS * UD;
-    if (__ballot(valid && ptgt < need) != 0) {
-      ptgt = ptgt > need ? ptgt : need;
-      __syncthreads();
-    }
+    // the generators' refill decision, restated: positions below ptgt are in the ring now
+    ptgt = v3_quota(ptgt, rd_start, ci);
+    // The lane throttle. A chunk reads at most [rd, rd + UHS * UD), so a lane parses the next chunk
+    // only if all of that is generated; otherwise it sits the chunk out under one divergent branch,
+    // with every piece of its state (rd, pend, prod, x, the flags) kept and still live, and
+    // publishes the same rd again. Progress: a throttled lane's rd does not move, so neither does
+    // its cap rd + UCAP, and from the next chunk on (rd_start = rd) its target grows by the quota
+    // (>= G > 0) per chunk until it is rd + UCAP >= rd + UHS * UD: the lane resumes after at most
+    // UHS * UD / quota + 2 chunks, and __ballot(live) cannot spin. Cost at the C3 rates, quota 21:
+    // 1,486 -> 1,536 rounds per wave, for 2,973 -> 2,700 generator passes
+    // (profiles/demand_throttle/ab_v3_quota.txt).
+    ok = ptgt >= rd + UHS * UD;
     rd_start = rd;
   }
 #ifdef MSC_PROF
@@ -266,6 +312,7 @@ __global__ __launch_bounds__(BS * (1 + G)) __attribute__((amdgpu_waves_per_eu(MS
     atomicAdd(&g_prof_v3[0], n_round);
     atomicAdd(&g_prof_v3[2], 1ull);
   }
+  if (n_thr) atomicAdd(&g_prof_v3[3], n_thr);
 #endif
   if (!valid) return;
   if constexpr (EA) {

@@ -6,7 +6,7 @@ register and scratch figures of every instantiation in the file.
   python tools/gen_loop_listing.py demand_v3.s [Li5ELi3ELb0E]
 
 The loop is the second innermost loop of the kernel that writes the ring twice (ds_write_b64): the
-first is the initial fill, the second the per-chunk refill, the third the top-up."""
+first is the initial fill, the second the per-chunk refill."""
 import re
 import sys
 
