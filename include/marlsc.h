@@ -513,6 +513,35 @@ int msc_mlp2_relu_forward_sampled(const float* x, int64_t n_rows, int32_t in_dim
                                   const float* pre1, int32_t pre1_group, const msc_gaussian_epilogue* sample,
                                   msc_stream_t stream);
 
+/* Per-agent policies in one launch: with parameter_sharing: false (the reference schema's default) every
+ * warehouse has its own RLModule (the policy mapping of ippo.py:106 / mappo.py:103), and the EnvRunner's
+ * _forward_inference (rlmodules/base.py:480-557) runs once per module. These entry points evaluate
+ * n_policies same-shaped MLPs with n_policies weight sets over rows laid out [n_rows / n_policies][n_policies]:
+ * row n belongs to policy n % n_policies. n_rows must be a multiple of n_policies, 1 <= n_policies <= 64.
+ * w1p / w2p / w3p are n_policies consecutive single-policy packs, each exactly as msc_mlp3_relu_forward
+ * (msc_mlp2_relu_forward) takes it, b1 / b2 / b3 n_policies consecutive bias vectors. x [n_rows][in_dim];
+ * pre1 (optional) [n_rows][hidden1], one row per row. sample may be NULL (means only, out required);
+ * with it out may be NULL, out_dim <= 8 (msc_mlp3_w3_layout(out_dim) == 1) as for the _sampled entry
+ * points, and log_std_rows must be 1 or n_policies (row p applies to policy p). Shape limits are the
+ * single-policy entry points'; a call that violates any condition returns an error and writes nothing.
+ * Nothing is read or written past n_rows rows.
+ *
+ * Contract. For every policy p, the outputs of rows p, p + n_policies, ... equal, bit for bit, what
+ * msc_mlp{3,2}_relu_forward[_sampled] returns for policy p's rows (x, pre1, eps) gathered contiguously,
+ * with policy p's pack and biases, pre1_group = 1 and log_std row p (the kernels are the same templates,
+ * with rows addressed at stride n_policies). So msc_mlp3_relu_forward's exactness and non-finite
+ * paragraphs hold per policy: integer data under the 2^24 headroom condition gives the integer
+ * evaluation bit for bit, and a row holding NaN or +-Inf changes no other row, of its own policy or of
+ * another. The result does not depend on the block order (MSC_MULTI_ORDER = 0 policy-major, 1
+ * policy-minor, the default; read at each launch) or on where blocks are placed. */
+int msc_mlp3_relu_multi(const float* x, int64_t n_rows, int32_t n_policies, int32_t in_dim, int32_t hidden1,
+                        int32_t hidden2, int32_t out_dim, const float* w1p, const float* b1, const float* w2p,
+                        const float* b2, const float* w3p, const float* b3, float* out, const float* pre1,
+                        const msc_gaussian_epilogue* sample, msc_stream_t stream);
+int msc_mlp2_relu_multi(const float* x, int64_t n_rows, int32_t n_policies, int32_t in_dim, int32_t hidden,
+                        int32_t out_dim, const float* w1p, const float* b1, const float* w3p, const float* b3, float* out,
+                        const float* pre1, const msc_gaussian_epilogue* sample, msc_stream_t stream);
+
 /* Wide-output policy inference: the centralised (CPPO) actor maps the global observation to the joint
  * action, n_warehouses * L -> hidden -> n_warehouses * n_skus (the reference's src/algorithms/cppo.py
  * builds it with MLPArchitecture.build, architectures/mlp.py:14-60; 40 outputs at C3, 80 at C5).

@@ -1086,6 +1086,57 @@ int msc_mlp2_relu_forward_sampled(const float* x, int64_t n_rows, int32_t in_dim
   return mlp2_impl(x, n_rows, in_dim, hidden, out_dim, w1p, b1, w3p, b3, out, pre1, pre1_group, sample, stream);
 }
 
+// per-agent policies in one launch (mlp_multi.hip): the single-policy entry points' argument checks,
+// then the multi-policy ones; hidden2 = 0 is the one-hidden-layer form
+static int mlp_multi_impl(const float* x, int64_t n_rows, int32_t n_policies, int32_t in_dim, int32_t hidden1,
+                          int32_t hidden2, int32_t out_dim, const float* w1p, const float* b1, const float* w2p,
+                          const float* b2, const float* w3p, const float* b3, float* out, const float* pre1,
+                          const msc_gaussian_epilogue* sample, msc_stream_t stream) {
+  const bool two = hidden2 != 0;
+  if (((uintptr_t)b1 | (uintptr_t)b2 | (uintptr_t)pre1 | (uintptr_t)w1p | (uintptr_t)w2p | (uintptr_t)w3p) & 15)
+    return set_err(-1, "b1, b2, pre1 and the packed weights must be 16-byte aligned");
+  if (!x || !w1p || !b1 || (two && (!w2p || !b2)) || !w3p || !b3 || (!out && !sample)) return set_err(-1, "null argument");
+  if (n_policies < 1 || n_policies > 64) return set_err(-1, "n_policies %d must be in 1..64", n_policies);
+  if (n_rows < 0 || n_rows % n_policies != 0)
+    return set_err(-1, "n_rows %lld must be a non-negative multiple of n_policies %d", (long long)n_rows, n_policies);
+  if (in_dim < 1 || in_dim > 1024 || out_dim < 1 || out_dim > 32)
+    return set_err(-1, "bad shape (n_rows %lld, in_dim %d, out_dim %d)", (long long)n_rows, in_dim, out_dim);
+  auto hs = [](int h) { return h == 64 || h == 128 || h == 256 || h == 512; };
+  if (two && !(hs(hidden1) && hs(hidden2)))
+    return set_err(-1, "hidden sizes %d, %d: the fused MLP supports [H1, H2] with H1, H2 in {64, 128, 256, 512}", hidden1, hidden2);
+  if (!two && !mlp2_supported(hidden1))
+    return set_err(-1, "hidden size %d: the fused MLP supports multiples of 32 up to 1024", hidden1);
+  MlpSample sm{};
+  if (const int r = mlp_sample_args(sample, out_dim, &sm)) return r;
+  if (sample && sample->log_std_rows != 1 && sample->log_std_rows != n_policies)
+    return set_err(-1, "log_std_rows %d must be 1 or n_policies %d", sample->log_std_rows, n_policies);
+  const int64_t E = n_rows / n_policies;
+  if (((E + 31) / 32 + 3) / 4 * n_policies > 0x7fffffff) return set_err(-1, "n_rows %lld: too many rows for one launch", (long long)n_rows);
+  if (two)
+    HIP_TRY(launch_mlp3_relu_multi(x, E, n_policies, in_dim, hidden1, hidden2, out_dim, w1p, b1, w2p, b2, w3p, b3, out,
+                                   pre1, (hipStream_t)stream, sample ? &sm : nullptr));
+  else
+    HIP_TRY(launch_mlp2_relu_multi(x, E, n_policies, in_dim, hidden1, out_dim, w1p, b1, w3p, b3, out, pre1,
+                                   (hipStream_t)stream, sample ? &sm : nullptr));
+  return 0;
+}
+
+int msc_mlp3_relu_multi(const float* x, int64_t n_rows, int32_t n_policies, int32_t in_dim, int32_t hidden1,
+                        int32_t hidden2, int32_t out_dim, const float* w1p, const float* b1, const float* w2p,
+                        const float* b2, const float* w3p, const float* b3, float* out, const float* pre1,
+                        const msc_gaussian_epilogue* sample, msc_stream_t stream) {
+  if (hidden2 == 0) return set_err(-1, "hidden2 must be one of {64, 128, 256, 512} (one hidden layer: msc_mlp2_relu_multi)");
+  return mlp_multi_impl(x, n_rows, n_policies, in_dim, hidden1, hidden2, out_dim, w1p, b1, w2p, b2, w3p, b3, out, pre1,
+                        sample, stream);
+}
+
+int msc_mlp2_relu_multi(const float* x, int64_t n_rows, int32_t n_policies, int32_t in_dim, int32_t hidden,
+                        int32_t out_dim, const float* w1p, const float* b1, const float* w3p, const float* b3, float* out,
+                        const float* pre1, const msc_gaussian_epilogue* sample, msc_stream_t stream) {
+  return mlp_multi_impl(x, n_rows, n_policies, in_dim, hidden, 0, out_dim, w1p, b1, nullptr, nullptr, w3p, b3, out, pre1,
+                        sample, stream);
+}
+
 // wide-output MLPs (the centralised actor, cppo.py: MLPArchitecture.build over the global observation
 // to the joint action): multi-tile MFMA output layer, optional LDS-staged sampling epilogue
 int msc_mlp_wide_supported(int32_t hidden1, int32_t hidden2, int32_t out_dim) {

@@ -248,6 +248,15 @@ hipError_t launch_mlp2_relu(const float* x, int64_t n, int L, int H1, int KO, co
                             const float* w3p, const float* b3, float* out, const float* pre1, int grp, hipStream_t st,
                             const MlpSample* smp = nullptr);
 bool mlp2_supported(int H1);
+// mlp_multi.hip: NP same-shaped policies over rows [E][NP] in one launch (weights / biases: NP
+// consecutive single-policy packs / vectors; pre1 one row per row; smp->ls_rows 1 or NP)
+hipError_t launch_mlp3_relu_multi(const float* x, int64_t E, int NP, int L, int H1, int H2, int KO, const float* w1p,
+                                  const float* b1, const float* w2p, const float* b2, const float* w3p, const float* b3,
+                                  float* out, const float* pre1, hipStream_t st, const MlpSample* smp);
+hipError_t launch_mlp2_relu_multi(const float* x, int64_t E, int NP, int L, int H1, int KO, const float* w1p,
+                                  const float* b1, const float* w3p, const float* b3, float* out, const float* pre1,
+                                  hipStream_t st, const MlpSample* smp);
+int mlp_multi_order();  // MSC_MULTI_ORDER: 0 policy-major, 1 (default) policy-minor block order
 // mlp_wide.hip: the multi-tile MFMA output layer (out_dim <= 128) with the LDS-staged sampling epilogue
 bool mlp_wide_supported(int H1, int H2, int KO);  // H2 = 0: one hidden layer
 hipError_t launch_mlp3_wide(const float* x, int64_t n, int L, int H1, int H2, int KO, const float* w1p, const float* b1,

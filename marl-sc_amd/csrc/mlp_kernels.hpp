@@ -107,7 +107,16 @@ __device__ __forceinline__ void musigma_row(const MlpMuSigma& e, int64_t j, int 
 // Linear is folded into the heads -- KO actions, 2 VKO per-lane sums (mu, then sigma) over the same
 // hidden-unit order, b3 = [b_mu | b_sigma] (2 KO), the packed weights [NT2 * 16][2][8 or 16] floats
 // (mlp_head_stride: mu's in the first half, sigma's in the second), musigma_row as the epilogue.
-template <int NT1, int NT2, int P, int WPE, int VKO, bool IL = false, class EP = MlpSample>
+// MULTI (mlp_multi.hip): grp same-shaped policies with grp weight sets in one launch over rows laid out
+// [n envs][grp policies] (row e grp + pol belongs to policy pol). A block serves 4 env tiles of one
+// policy -- the VALU output layer stages that policy's w3 slice in LDS -- and a wave's 32 rows are
+// envs 32 tile .. 32 tile + 31 of it, so every row array is addressed with row stride grp and every
+// weight / bias array is offset by pol single-policy sizes; log_std row pol applies (sample_row's
+// j % ls_rows, ls_rows = grp or 1), pre1 is one row per row. prio bit 1 is the block order: clear =
+// policy-major (a policy's blocks consecutive), set = policy-minor (pol = block % grp: with grp a
+// multiple of 8 a policy's blocks are congruent mod 8). The arithmetic per row is the single-policy
+// kernel's, operation for operation. MULTI = false compiles to the single-policy kernel as it was.
+template <int NT1, int NT2, int P, int WPE, int VKO, bool IL = false, class EP = MlpSample, bool MULTI = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void mlp3_relu_kernel(
     const float* __restrict__ x, int64_t n, int L, int KS1, const float4* __restrict__ w1p, const float* __restrict__ b1,
     const float4* __restrict__ w2p, const float* __restrict__ b2, const float4* __restrict__ w3p,
@@ -122,17 +131,29 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
   constexpr int S4 = NT1 * 4;  // layer-2 k steps of 4 MFMAs (2 hidden units each)
   // the policy forward is on the rollout's critical path (step t + 1 needs its actions), the
   // pipelined demand kernel of step t + 1 (priorities 1-2) is not: issue ahead of it
-  if (prio) __builtin_amdgcn_s_setprio(3);
+  if (MULTI ? (prio & 1) : prio) __builtin_amdgcn_s_setprio(3);
   const int lane = threadIdx.x & 63, h = lane >> 5;
-  const int64_t tile = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  int64_t tile = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  int64_t pol = 0;
+  if constexpr (MULTI) {  // n envs x grp policies: this block's policy and its 4 env tiles
+    const unsigned nb = (unsigned)(((n + 31) / 32 + 3) / 4), np = (unsigned)grp;  // blocks per policy
+    const unsigned be = (prio & 2) ? blockIdx.x / np : blockIdx.x % nb;
+    pol = (prio & 2) ? blockIdx.x % np : blockIdx.x / nb;
+    tile = (int64_t)be * 4 + (threadIdx.x >> 6);
+    w1p += pol * (NT1 * ((KS1 + 3) / 4) * 64), b1 += pol * (NT1 * 32);
+    w2p += pol * (NT2 * S4 * 64), b2 += pol * (NT2 * 32);
+    w3p += pol * (VKO > 0 ? NT2 * 16 * 2 * F4 : NT2 * 4 * 64), b3 += pol * KO;
+  }
   __shared__ float4 w3s[VKO > 0 ? NT2 * 16 * 2 * F4 : 1];  // [s][h][8 floats] (16 for a dual head wider than 4)
   if constexpr (VKO > 0) {
     for (int i = threadIdx.x; i < NT2 * 16 * 2 * F4; i += blockDim.x) w3s[i] = w3p[i];
     __syncthreads();
   }
   if (tile * 32 >= n) return;  // wave-uniform (no block-level synchronisation below)
-  const int64_t j = tile * 32 + (lane & 31);
-  const bool jv = j < n;
+  const int64_t e = tile * 32 + (lane & 31);
+  const int64_t j = MULTI ? e * grp + pol : e;  // the lane's row
+  const bool jv = e < n;
+  if constexpr (MULTI) grp = 1;  // pre1: one row per row
   const int M4 = (KS1 + 3) / 4;  // layer-1 k steps of 4 MFMAs
 
   // layer 1: H1^T = W1 X^T + b1 (+ pre1 of the sample's group); lane half h feeds features
@@ -367,7 +388,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 // folded into the output accumulators as soon as it is final, so any hidden size up to 1024 runs
 // with 16 TB accumulator registers. VKO > 0: output layer on the VALU (weights in LDS), else on
 // the MFMA (fragments from L2, KO <= 32 rows). EP = MlpMuSigma: the dual head, as in mlp3_relu_kernel.
-template <int TB, int WPE, int VKO, class EP = MlpSample>
+// MULTI: as in mlp3_relu_kernel.
+template <int TB, int WPE, int VKO, class EP = MlpSample, bool MULTI = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void mlp2_relu_kernel(
     const float* __restrict__ x, int64_t n, int L, int KS1, int NT1, const float4* __restrict__ w1p,
     const float* __restrict__ b1, const float4* __restrict__ w3p, const float* __restrict__ b3, int KO,
@@ -377,17 +399,28 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
   static_assert(!HEAD || VKO > 0, "the dual head runs on the VALU output layer");
   constexpr int F4 = HEAD && VKO > 4 ? 4 : 2;  // float4 per (hidden pair, lane half) in LDS
   constexpr int NO = HEAD ? 2 * VKO : VKO;     // per-lane output sums
-  if (prio) __builtin_amdgcn_s_setprio(3);
+  if (MULTI ? (prio & 1) : prio) __builtin_amdgcn_s_setprio(3);
   const int lane = threadIdx.x & 63, h = lane >> 5;
-  const int64_t tile = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  int64_t tile = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  int64_t pol = 0;
+  if constexpr (MULTI) {  // n envs x grp policies: this block's policy and its 4 env tiles
+    const unsigned nb = (unsigned)(((n + 31) / 32 + 3) / 4), np = (unsigned)grp;  // blocks per policy
+    const unsigned be = (prio & 2) ? blockIdx.x / np : blockIdx.x % nb;
+    pol = (prio & 2) ? blockIdx.x % np : blockIdx.x / nb;
+    tile = (int64_t)be * 4 + (threadIdx.x >> 6);
+    w1p += pol * (NT1 * ((KS1 + 3) / 4) * 64), b1 += pol * (NT1 * 32);
+    w3p += pol * (VKO > 0 ? NT1 * 16 * 2 * F4 : NT1 * 4 * 64), b3 += pol * KO;
+  }
   extern __shared__ float4 w3d[];  // VALU output layer: [NT1 * 16][2][8 floats] (16 for a dual head wider than 4)
   if constexpr (VKO > 0) {
     for (int i = threadIdx.x; i < NT1 * 16 * 2 * F4; i += blockDim.x) w3d[i] = w3p[i];
     __syncthreads();
   }
   if (tile * 32 >= n) return;  // wave-uniform
-  const int64_t j = tile * 32 + (lane & 31);
-  const bool jv = j < n;
+  const int64_t e = tile * 32 + (lane & 31);
+  const int64_t j = MULTI ? e * grp + pol : e;  // the lane's row
+  const bool jv = e < n;
+  if constexpr (MULTI) grp = 1;  // pre1: one row per row
   const int M4 = (KS1 + 3) / 4;
   const float* xr = x + (jv ? j : 0) * (int64_t)L;
   const float* pg = pre1 != nullptr ? pre1 + ((jv ? j : 0) / grp) * (int64_t)(NT1 * 32) : nullptr;

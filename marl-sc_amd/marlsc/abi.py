@@ -178,6 +178,10 @@ def lib() -> C.CDLL:
                                      vp, vp, C.c_int32, P(MscGaussianEpilogue), vp]
     L.msc_mlp2_relu_wide.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp, C.c_int32,
                                      P(MscGaussianEpilogue), vp]
+    L.msc_mlp3_relu_multi.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp,
+                                      vp, vp, vp, vp, vp, P(MscGaussianEpilogue), vp]
+    L.msc_mlp2_relu_multi.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp,
+                                      P(MscGaussianEpilogue), vp]
     L.msc_reward_team_sum.argtypes = [vp, C.c_int64, C.c_int32, vp, vp, vp]
     L.msc_gru_supported.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     L.msc_gru_step.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, P(MscGruWeights), C.c_int32,
@@ -212,7 +216,8 @@ EXPORTED_SYMBOLS = [
     "msc_env_set_episode_counters", "msc_gae", "msc_adv_normalize", "msc_gae_grouped", "msc_adv_normalize_grouped", "msc_ppo_loss_workspace", "msc_ppo_loss", "msc_gaussian_sample", "msc_mlp3_w3_layout", "msc_mlp3_relu_forward", "msc_mlp2_relu_forward",
     "msc_mlp3_relu_forward_sampled", "msc_mlp2_relu_forward_sampled",
     "msc_mlp_musigma_layout", "msc_mlp3_relu_musigma", "msc_mlp2_relu_musigma",
-    "msc_mlp_wide_supported", "msc_mlp3_relu_wide", "msc_mlp2_relu_wide", "msc_reward_team_sum",
+    "msc_mlp_wide_supported", "msc_mlp3_relu_wide", "msc_mlp2_relu_wide", "msc_mlp3_relu_multi", "msc_mlp2_relu_multi",
+    "msc_reward_team_sum",
     "msc_gru_supported", "msc_gru_step",
     "msc_policy_create", "msc_policy_act", "msc_policy_set_tables", "msc_policy_destroy",
     "msc_normal_keyed", "msc_poisson_draws", "msc_gen_draws", "msc_meanstd_scratch_doubles", "msc_meanstd_filter", "msc_seedseq_u32", "msc_last_error", "msc_abi_version",

@@ -188,7 +188,7 @@ class CentralizedActorCritic(MultiAgentActorCritic):
     policy only; a single policy is the same case (every row is its row), so it is taken here too."""
 
     def __init__(self, obs_dim: int, action_dim: int, rc: RolloutConfig):
-        super().__init__(1, obs_dim, 0, action_dim, rc, False)
+        super().__init__(1, obs_dim, 0, action_dim, rc, False, multi_mlp=False)  # one policy: nothing to batch
 
     def actor_sample_x(self, x: torch.Tensor, sample) -> bool:
         return fused_actor_sample(self.policies[0].actor, x, sample)

@@ -19,6 +19,10 @@ dual-head output layer (msc_mlp{2,3}_relu_musigma, csrc/mlp_musigma.hip), and ne
 outputs (the centralised CPPO actor) have a multi-tile output layer with its own sampling epilogue
 (msc_mlp{2,3}_relu_wide, csrc/mlp_wide.hip): see the sections at the end of this file.
 
+With one policy per agent (parameter_sharing: false) the W same-shaped actors, and the W critics, run as
+one launch each over the rows [..., W, L] (msc_mlp{2,3}_relu_multi, csrc/mlp_multi.hip; multi_forward at
+the end of this file; opt-in, MSC_MULTI_MLP=1).
+
 There is no CPU fallback: a CUDA tensor on a build without libmarlsc raises (abi.lib()).
 """
 from __future__ import annotations
@@ -565,4 +569,142 @@ def wide_forward(mods, x: torch.Tensor, out: Optional[torch.Tensor] = None, *, s
         b2 = l2.bias.detach().float().contiguous()
         abi.check(abi.lib().msc_mlp3_relu_wide(vp(xf), n, L, l1.out_features, l2.out_features, KO, vp(w1p), vp(b1),
                                                vp(w2p), vp(b2), vp(w3p), vp(b3), vp(out), vp(pre1), int(group), ep, st))
+    return None if out is None else out.reshape(*lead, KO)
+
+
+# ----------------------------------------------------------------------------------------------
+# Per-agent policies (parameter_sharing: false, one module per warehouse): P same-shaped MLPs with P
+# weight sets over rows laid out [..., P, L] in one launch, msc_mlp{2,3}_relu_multi (csrc/mlp_multi.hip).
+# Row (e, p) is bit-identical to mlp3_forward on policy p's rows gathered contiguously. Opt-in at
+# rollout (MSC_MULTI_MLP=1 / MultiAgentActorCritic(multi_mlp=True)); multi_forward itself does not look
+# at the switch. Not covered: GRU policies, mu/sigma-head actors, the wide (33..128 outputs) kernel.
+# ----------------------------------------------------------------------------------------------
+MULTI_MAX_POLICIES = 64
+
+
+def multi_default() -> bool:
+    """MSC_MULTI_MLP=1 turns the multi-policy kernel on where MultiAgentActorCritic is built with
+    multi_mlp=None. Off by default: see DESIGN.md section 8 for the measured A/B and the rule for a flip."""
+    return os.environ.get("MSC_MULTI_MLP", "0") == "1"
+
+
+def multi_layers(mods_list) -> int:
+    """2 or 3 when every layer list of mods_list passes fused_layers with the same form and the same
+    Linear shapes (1..64 policies); 0 otherwise (the caller runs the policies one by one)."""
+    mods_list = [list(m) for m in mods_list]
+    if not 1 <= len(mods_list) <= MULTI_MAX_POLICIES:
+        return 0
+    nl = fused_layers(mods_list[0])
+    if nl == 0:
+        return 0
+    shapes = [tuple(m.weight.shape) for m in mods_list[0][0::2]]
+    for mods in mods_list[1:]:
+        if fused_layers(mods) != nl or [tuple(m.weight.shape) for m in mods[0::2]] != shapes:
+            return 0
+    return nl
+
+
+def pack_multi(w1s, w2s, w3s, layout: Optional[int] = None):
+    """P policies' torch Linear weights (lists of [H1, L], [H2, H1] or None, [KO, H2]) -> (w1p, w2p, w3p),
+    each [P, ...]: row p is pack_mlp3 of policy p (one gather over the stacked weights with the
+    cached index maps)."""
+    H1, L = w1s[0].shape
+    H2, KO = (w2s[0].shape[0] if w2s is not None else 0), w3s[0].shape[0]
+    i1, v1, i2, i3, v3 = _index_maps(L, H1, H2, KO, w1s[0].device, w3_layout(KO) if layout is None else layout)
+    n = len(w1s)
+    zero = torch.zeros((), device=w1s[0].device, dtype=torch.float32)
+    flat = lambda ws: torch.stack([w.detach().float() for w in ws]).reshape(n, -1)  # noqa: E731
+    w1p = torch.where(v1, flat(w1s)[:, i1], zero)
+    w2p = flat(w2s)[:, i2].contiguous() if w2s is not None else None
+    w3p = torch.where(v3, flat(w3s)[:, i3], zero)
+    return w1p.contiguous(), w2p, w3p.contiguous()
+
+
+def multi_pack(mods_list, w1s=None, cur=None):
+    """(w1p, w2p, w3p, b1, b2, b3) of P policies: stacked packs [P, ...] and stacked biases [P, H] (w2p /
+    b2 None for one hidden layer), cached on policy 0's first Linear under a key holding every
+    policy's (data_ptr, _version) of every weight and bias: rebuilt when any one of them changes or
+    moves, and only then. w1s: first-layer weights to use instead of each mods[0].weight. cur: the
+    stream the pack is used on (_cached_pack's ordering); None on the host."""
+    mods_list = [list(m) for m in mods_list]
+    nl = multi_layers(mods_list)
+    if nl == 0:
+        raise ValueError("no multi-policy kernel for these layer sequences (see multi_layers)")
+    l1 = mods_list[0][0]
+    w1s = [m[0].weight for m in mods_list] if w1s is None else list(w1s)
+    w2s = [m[2].weight for m in mods_list] if nl == 3 else None
+    w3s = [m[-1].weight for m in mods_list]
+    lins = [[m for m in mods[0::2]] for mods in mods_list]
+    weights = tuple(w1s) + tuple(w2s or ()) + tuple(w3s) + tuple(m.bias for ls in lins for m in ls)
+
+    def build():
+        w1p, w2p, w3p = pack_multi(w1s, w2s, w3s)
+        bs = [torch.stack([ls[i].bias.detach().float() for ls in lins]).contiguous() for i in range(nl)]
+        return (w1p, w2p, w3p, bs[0], bs[1] if nl == 3 else None, bs[-1])
+
+    slot = ("multi", len(mods_list), w1s[0].shape, w1s[0].stride(), w1s[0].storage_offset())
+    if cur is not None:
+        return _cached_pack(l1, slot, weights, cur, build)
+    packs = getattr(l1, "_msc_packs", None)
+    if packs is None:
+        packs = l1._msc_packs = {}
+    pk = packs.setdefault(slot, _Pack())
+    key = tuple((p.data_ptr(), p._version) for p in weights)
+    if pk.key != key:
+        pk.tensors, pk.key = build(), key
+    return pk.tensors
+
+
+def multi_forward(mods_list, x: torch.Tensor, out: Optional[torch.Tensor] = None, *, w1=None,
+                  pre1: Optional[torch.Tensor] = None, sample=None) -> Optional[torch.Tensor]:
+    """msc_mlp{2,3}_relu_multi over x [..., P, L] (f32 CUDA) -> [..., P, KO]: policy p (mods_list[p], as
+    accepted by multi_layers) evaluates the rows x[..., p, :], all in one launch.
+    w1: a list of first-layer weights to use instead of each policy's mods[0].weight; pre1 [rows, H1]:
+    added to the first layer's pre-activation, one row per row; sample: (log_std [1 or P, KO],
+    logstd_floor, eps, actions, logp, clipped) -- msc_gaussian_sample in the epilogue, log_std row p for
+    policy p (needs the VALU output layer, KO <= 8); the means then go to `out` only when it is given
+    (returns `out`, possibly None)."""
+    mods_list = [list(m) for m in mods_list]
+    nl = multi_layers(mods_list)
+    if nl == 0:
+        raise ValueError("no multi-policy kernel for these layer sequences (see multi_layers)")
+    NP = len(mods_list)
+    l1, l3 = mods_list[0][0], mods_list[0][-1]
+    H1, KO = l1.out_features, l3.out_features
+    H2 = mods_list[0][2].out_features if nl == 3 else 0
+    L = l1.in_features if w1 is None else w1[0].shape[1]
+    if x.dim() < 2 or x.shape[-2] != NP or x.shape[-1] != L:
+        raise ValueError(f"input must be [..., {NP}, {L}], not {tuple(x.shape)}")
+    cur = torch.cuda.current_stream(x.device)
+    w1p, w2p, w3p, b1, b2, b3 = multi_pack(mods_list, w1, cur)
+    lead, xf = x.shape[:-1], _rows(x, L)
+    n = xf.shape[0]
+    if pre1 is not None:
+        pre1 = pre1.float().contiguous()
+        if pre1.shape != (n, H1):
+            raise ValueError(f"pre1 must be [{n}, {H1}]")
+    vp = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+    ep = None
+    if sample is not None:
+        ls, floor, eps, act, logp, clipped = sample
+        for t in (ls, eps, act, logp, clipped):
+            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+                raise ValueError("sampling buffers must be contiguous float32 CUDA tensors")
+        if eps.numel() != n * KO or act.numel() != n * KO or clipped.numel() != n * KO or logp.numel() != n \
+                or ls.dim() != 2 or ls.shape[1] != KO or ls.shape[0] not in (1, NP):
+            raise ValueError("sampling buffers do not match the MLPs' rows / outputs / policies")
+        ep = C.byref(abi.MscGaussianEpilogue(vp(ls), int(ls.shape[0]), C.c_float(floor), vp(eps), vp(act), vp(logp),
+                                             vp(clipped)))
+    elif out is None:
+        out = torch.empty((n, KO), device=x.device, dtype=torch.float32)
+    if out is not None and not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
+                                and out.numel() == n * KO):
+        raise ValueError("out must be a contiguous float32 CUDA tensor of rows x outputs")
+    st = C.c_void_p(cur.cuda_stream)
+    if nl == 2:
+        abi.check(abi.lib().msc_mlp2_relu_multi(vp(xf), n, NP, L, H1, KO, vp(w1p), vp(b1), vp(w3p), vp(b3), vp(out),
+                                                vp(pre1), ep, st))
+    else:
+        abi.check(abi.lib().msc_mlp3_relu_multi(vp(xf), n, NP, L, H1, H2, KO, vp(w1p), vp(b1), vp(w2p), vp(b2), vp(w3p),
+                                                vp(b3), vp(out), vp(pre1), ep, st))
     return None if out is None else out.reshape(*lead, KO)

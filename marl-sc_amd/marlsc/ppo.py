@@ -51,6 +51,7 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from . import dist as mdist
+from . import mlp as mlp3
 from .ppo_loss import STAT_KEYS, fused_loss_default, fused_ppo_loss
 from .rollout import (LOG_STD_MIN, PolicyNets, RecurrentAPI, RolloutCollector, RolloutConfig, check_gru_config,
                       check_head_config, fused_actor_sample, gaussian_sample, head_sample, mlp_forward, network_types,
@@ -175,12 +176,17 @@ class MultiAgentActorCritic(RecurrentAPI, nn.Module):
     is threaded through RecurrentAPI's initial_state / step / sequence."""
 
     def __init__(self, n_agents: int, local_obs_dim: int, global_obs_dim: int, action_dim: int, rc: RolloutConfig,
-                 shared: bool):
+                 shared: bool, multi_mlp: Optional[bool] = None):
+        """multi_mlp: per-agent MLP policies (not shared, not recurrent, no mu/sigma head) run their W
+        actors, and their W critics, as one msc_mlp{2,3}_relu_multi launch each at inference instead of W
+        torch layer sequences (mlp.multi_forward); None reads MSC_MULTI_MLP (default off). Anything the
+        kernel does not cover keeps the torch path."""
         super().__init__()
         self.rc, self.shared, self.W = rc, bool(shared), int(n_agents)
         self.policies = nn.ModuleList([AgentModule(local_obs_dim, global_obs_dim, action_dim, rc)
                                        for _ in range(1 if shared else n_agents)])
         self.head_mode = bool(rc.use_mu_sigma_head)
+        self.multi_mlp = mlp3.multi_default() if multi_mlp is None else bool(multi_mlp)
 
     def _x(self, local_obs, full_obs, kind):
         return full_obs if kind == "global" else local_obs
@@ -188,9 +194,25 @@ class MultiAgentActorCritic(RecurrentAPI, nn.Module):
     def _policy_list(self):
         return list(self.policies)
 
+    def _multi(self, nets, x: torch.Tensor) -> int:
+        """multi_layers of the per-agent networks `nets` when one multi-policy launch over x applies (the
+        switch is on, per-agent MLP policies without a head, f32 CUDA input, no autograd); else 0."""
+        if not self.multi_mlp or self.shared or self.recurrent or self.head_mode:
+            return 0
+        if not (x.is_cuda and x.dtype == torch.float32 and not torch.is_grad_enabled()):
+            return 0
+        return mlp3.multi_layers(nets)
+
     def actor_sample_x(self, x: torch.Tensor, sample) -> bool:
         """actor_sample on the actor's own input x (the trunk's features with shared layers)."""
-        return self.shared and fused_actor_sample(self.policies[0].actor, x, sample)
+        if self.shared:
+            return fused_actor_sample(self.policies[0].actor, x, sample)
+        if self.multi_mlp:
+            actors = [list(p.actor) for p in self.policies]
+            if self._multi(actors, x) and mlp3.w3_layout(actors[0][-1].out_features) == 1:
+                mlp3.multi_forward(actors, x, None, sample=sample)  # W actors + sampling in one launch
+                return True
+        return False
 
     def sample_actions_x(self, x, eps, actions, logp) -> torch.Tensor:
         if self.shared:
@@ -199,6 +221,10 @@ class MultiAgentActorCritic(RecurrentAPI, nn.Module):
         return gaussian_sample(mu.contiguous(), ls.contiguous(), LOG_STD_MIN, eps, actions, logp)
 
     def actor_mean_x(self, x: torch.Tensor) -> torch.Tensor:
+        if self.multi_mlp and not self.shared:
+            actors = [list(p.actor) for p in self.policies]
+            if self._multi(actors, x):
+                return mlp3.multi_forward(actors, x)
         return self._per_agent(lambda p, v: p.actor(v), x)
 
     def sample_dist_x(self, x: torch.Tensor):
@@ -253,12 +279,34 @@ class MultiAgentActorCritic(RecurrentAPI, nn.Module):
         if self.rc.critic_obs_type == "global" and full_obs is None:  # split first layer (rollout.py)
             if self.shared:
                 return split_global_mlp(self.policies[0].critic, local_obs, out=out).squeeze(-1)
+            critics = [list(p.critic) for p in self.policies] if self.multi_mlp else None
+            if critics and self._multi(critics, local_obs):
+                # split_global_mlp for W critics: the global blocks of all W first layers as one GEMM over
+                # the E env rows ([E, W L] x [W L, W H1] -> one pre1 row per (env, agent)), the local
+                # blocks and everything after them in one multi-policy launch
+                W, L = local_obs.shape[-2], local_obs.shape[-1]
+                H1 = critics[0][0].out_features
+                wg = torch.cat([c[0].weight[:, L:] for c in critics])  # [W H1, W L]
+                g = torch.nn.functional.linear(local_obs.reshape(-1, W * L), wg).view(-1, H1)
+                return mlp3.multi_forward(critics, local_obs, _values_rows(out, local_obs),
+                                          w1=[c[0].weight[:, :L] for c in critics], pre1=g).squeeze(-1)
             return torch.stack([split_global_mlp(p.critic, local_obs, w).squeeze(-1)
                                 for w, p in enumerate(self.policies)], dim=-1)
         x = self._x(local_obs, full_obs, self.rc.critic_obs_type)
         if self.shared:
             return mlp_forward(self.policies[0].critic, x, out=out).squeeze(-1)
+        critics = [list(p.critic) for p in self.policies] if self.multi_mlp else None
+        if critics and self._multi(critics, x):
+            return mlp3.multi_forward(critics, x, _values_rows(out, x)).squeeze(-1)
         return torch.stack([p.critic(x[..., w, :]).squeeze(-1) for w, p in enumerate(self.policies)], dim=-1)
+
+
+def _values_rows(out: Optional[torch.Tensor], x: torch.Tensor) -> Optional[torch.Tensor]:
+    """`out` as the multi-policy critic's [rows, 1] output buffer, or None when it cannot be one."""
+    rows = x[..., 0].numel()
+    if out is None or not out.is_cuda or not out.is_contiguous() or out.dtype != torch.float32 or out.numel() != rows:
+        return None
+    return out.view(rows, 1)
 
 
 def gaussian_logp(a: torch.Tensor, mean: torch.Tensor, log_std: torch.Tensor) -> torch.Tensor:
@@ -666,11 +714,14 @@ def compute_obs_statistics(env_config: Any, seed_manager, mode: str = "meanstd_c
 class PPOTrainer:
     def __init__(self, env_config: Any, cfg: PPOConfig, *, root_seed: int = 42, n_envs: Optional[int] = None,
                  rollout_len: Optional[int] = None, device: int = 0, env_meta: Optional[Dict[str, Any]] = None,
-                 eval_seed: Optional[int] = None):
+                 eval_seed: Optional[int] = None, multi_mlp: Optional[bool] = None):
+        """multi_mlp: passed to MultiAgentActorCritic (per-agent policies in one launch; None reads
+        MSC_MULTI_MLP)."""
         from .seeding import SeedManager
         from .spec import EnvSpec
         from .vec_env import VecInventoryEnv
         self.cfg = cfg
+        self.multi_mlp = multi_mlp
         self.rank, self.world = (dist.get_rank(), dist.get_world_size()) if (dist.is_available() and dist.is_initialized()) else (0, 1)
         self.root_seed = int(root_seed)
         self.sm = SeedManager(self.root_seed)
@@ -733,7 +784,7 @@ class PPOTrainer:
 
     def _build_module(self, rc: RolloutConfig) -> MultiAgentActorCritic:
         W, L = self.env.W, self.env.local_obs_dim
-        return MultiAgentActorCritic(W, L, L * W, self.env.K, rc, self.cfg.parameter_sharing)
+        return MultiAgentActorCritic(W, L, L * W, self.env.K, rc, self.cfg.parameter_sharing, multi_mlp=self.multi_mlp)
 
     def _full_fn(self):
         if self.cfg.actor_obs_type != "global" and not (self.module.recurrent and self.cfg.critic_obs_type == "global"):
