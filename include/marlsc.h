@@ -640,6 +640,28 @@ int msc_mlp2_relu_musigma(const float* x, int64_t n_rows, int32_t in_dim, int32_
                           const float* b1, const float* whp, const float* bh, const float* pre1, int32_t pre1_group,
                           const msc_musigma_epilogue* head, msc_stream_t stream);
 
+/* Diagnostic (no reference counterpart), without touching a GPU: the kernel instantiation and launch
+ * geometry the fused-MLP entry points of a family would pick under the current MSC_MLP_* knobs, for
+ * hidden sizes [hidden1, hidden2] (hidden2 = 0: one hidden layer), out_dim outputs (MSC_MLP_MUSIGMA: k
+ * actions) and n_rows rows (MSC_MLP_MULTI: of n_policies policies, which must divide n_rows; ignored by
+ * the other families). All forms of a family return the same bits, so this is what shows which one runs.
+ * Writes up to n of
+ *  {supported (0: the entry point would refuse these sizes, and every other value is 0),
+ *   NT1, NT2 (hidden tiles of 32 units; NT2 = 0 with one hidden layer), P (layer-2 tiles per pass),
+ *   waves per SIMD, IL (output layer interleaved into the next pass), output-layer width (VALU outputs of
+ *   the plain families, 0 = the MFMA output layer; per-head width of the mu/sigma head; output tiles of
+ *   the wide family), TB (hidden tiles per group with one hidden layer, else 0), dynamic LDS bytes,
+ *   grid blocks (of 256 threads)};
+ * returns the count written (MSC_MLP_PLAN_N at most), or < 0 for an unknown family or bad row /
+ * policy counts. */
+#define MSC_MLP_RELU 0    /* msc_mlp{3,2}_relu_forward[_sampled] */
+#define MSC_MLP_MULTI 1   /* msc_mlp{3,2}_relu_multi */
+#define MSC_MLP_MUSIGMA 2 /* msc_mlp{3,2}_relu_musigma */
+#define MSC_MLP_WIDE 3    /* msc_mlp{3,2}_relu_wide */
+#define MSC_MLP_PLAN_N 10
+int msc_mlp_plan(int32_t family, int32_t hidden1, int32_t hidden2, int32_t out_dim, int64_t n_rows, int32_t n_policies,
+                 int32_t* out, int32_t n);
+
 /* One time step of a GRU network for n_rows rows in one launch: replaces the module
  * GRUArchitecture.build returns (architectures/gru.py:14-85: nn.GRU(batch_first) -> output_proj =
  * [act,] Linear [, act]) as BaseRLModule._forward_gru steps it on a [B, obs_dim] input

@@ -18,6 +18,7 @@
 #include "../../include/marlsc.h"
 #include "env.hpp"
 #include "env_plan.hpp"
+#include "mlp_dispatch.hpp"
 #include "rng.hpp"
 
 using namespace msc;
@@ -1004,34 +1005,96 @@ int msc_meanstd_filter(const float* obs, float* out, int64_t n_rows, int32_t n_c
 
 int msc_mlp3_w3_layout(int32_t out_dim) { return out_dim >= 1 && out_dim <= 32 ? (mlp3_valu_outputs(out_dim) > 0 ? 1 : 0) : -1; }
 
-static int mlp_sample_args(const msc_gaussian_epilogue* g, int out_dim, MlpSample* sm) {
+// what an MLP entry point is, for the one argument check and the one body of the ten
+struct MlpEntry {
+  const char* word;       // the family in the hidden-size texts ("fused" / "wide"); nullptr: the mu/sigma head's own check
+  const char* one_layer;  // the entry point a call with hidden2 = 0 is sent to (nullptr: hidden2 = 0 is this one's form)
+  bool b2;                // the alignment text names b2 (every signature with a second hidden layer, and its sibling's)
+  int max_out;            // bound on out_dim (0: no out_dim; k is checked with the head)
+  bool multi;             // group is n_policies, not pre1_group
+};
+static const MlpEntry MLP3{"fused", nullptr, true, 32, false}, MLP2{"fused", nullptr, false, 32, false},
+    MLP_MULTI3{"fused", "msc_mlp2_relu_multi", true, 32, true}, MLP_MULTI2{"fused", nullptr, true, 32, true},
+    MLP_WIDE3{"wide", "msc_mlp2_relu_wide", true, 128, false}, MLP_WIDE2{"wide", nullptr, true, 128, false},
+    MLP_HEAD3{nullptr, "msc_mlp2_relu_musigma", true, 0, false}, MLP_HEAD2{nullptr, nullptr, false, 0, false};
+// and what it was called with (w3p / b3: the head's whp / bh; absent arguments 0)
+struct MlpCall {
+  const float* x;
+  int64_t n_rows;
+  int32_t in_dim, hidden1, hidden2, out_dim;
+  const float *w1p, *b1, *w2p, *b2, *w3p, *b3;
+  float* out;
+  const float* pre1;
+  int32_t group;  // pre1_group, or n_policies
+};
+
+// two: a second hidden layer is expected (w2p / b2, hidden sizes of the 64..512 set); sink: where the result goes (out,
+// or the epilogue that makes out optional)
+static int mlp_check(const MlpEntry& e, bool two, const MlpCall& a, const void* sink) {
+  if (!e.multi && a.pre1 && a.group < 1) return set_err(-1, "pre1_group %d must be >= 1", a.group);
+  // the kernel reads b1 / b2 / pre1 rows as float4
+  if (((uintptr_t)a.b1 | (uintptr_t)a.b2 | (uintptr_t)a.pre1 | (uintptr_t)a.w1p | (uintptr_t)a.w2p | (uintptr_t)a.w3p) & 15)
+    return set_err(-1, "b1, %spre1 and the packed weights must be 16-byte aligned", e.b2 ? "b2, " : "");
+  if (!a.x || !a.w1p || !a.b1 || (two && (!a.w2p || !a.b2)) || !a.w3p || !a.b3 || !sink) return set_err(-1, "null argument");
+  if (e.multi) {
+    if (a.group < 1 || a.group > 64) return set_err(-1, "n_policies %d must be in 1..64", a.group);
+    if (a.n_rows < 0 || a.n_rows % a.group != 0)
+      return set_err(-1, "n_rows %lld must be a non-negative multiple of n_policies %d", (long long)a.n_rows, a.group);
+    if (mlp_blocks(a.n_rows / a.group, a.group) > 0x7fffffff)
+      return set_err(-1, "n_rows %lld: too many rows for one launch", (long long)a.n_rows);
+  }
+  const bool rows_in = a.n_rows >= 0 && a.in_dim >= 1 && a.in_dim <= 1024;
+  if (e.max_out == 0 && !rows_in) return set_err(-1, "bad shape (n_rows %lld, in_dim %d)", (long long)a.n_rows, a.in_dim);
+  if (e.max_out != 0 && !(rows_in && a.out_dim >= 1 && a.out_dim <= e.max_out))
+    return set_err(-1, "bad shape (n_rows %lld, in_dim %d, out_dim %d)", (long long)a.n_rows, a.in_dim, a.out_dim);
+  if (e.one_layer && a.hidden2 == 0) return set_err(-1, "hidden2 must be one of {64, 128, 256, 512} (one hidden layer: %s)", e.one_layer);
+  if (e.word && two && !(mlp_hidden_ok(a.hidden1) && mlp_hidden_ok(a.hidden2)))
+    return set_err(-1, "hidden sizes %d, %d: the %s MLP supports [H1, H2] with H1, H2 in {64, 128, 256, 512}", a.hidden1, a.hidden2, e.word);
+  if (e.word && !two && !mlp2_supported(a.hidden1))
+    return set_err(-1, "hidden size %d: the %s MLP supports multiples of 32 up to 1024", a.hidden1, e.word);
+  return 0;
+}
+
+// need_valu: the family samples only on the VALU output layer; n_policies > 0: one log_std row, or one per policy
+static int mlp_sample_args(const msc_gaussian_epilogue* g, int out_dim, bool need_valu, int n_policies, MlpSample* sm) {
   if (!g) return 0;
   if (!g->log_std || !g->eps || !g->actions || !g->logp || !g->clipped) return set_err(-1, "null sampling buffer");
   if (g->log_std_rows < 1) return set_err(-1, "log_std_rows %d must be >= 1", g->log_std_rows);
-  if (mlp3_valu_outputs(out_dim) == 0)
+  if (need_valu && mlp3_valu_outputs(out_dim) == 0)
     return set_err(-1, "sampling epilogue needs the VALU output layer (out_dim %d <= 8)", out_dim);
+  if (n_policies > 0 && g->log_std_rows != 1 && g->log_std_rows != n_policies)
+    return set_err(-1, "log_std_rows %d must be 1 or n_policies %d", g->log_std_rows, n_policies);
   *sm = MlpSample{g->log_std, g->log_std_rows, g->logstd_floor, g->eps, g->actions, g->logp, g->clipped};
   return 0;
 }
 
-static int mlp3_impl(const float* x, int64_t n_rows, int32_t in_dim, int32_t hidden1, int32_t hidden2, int32_t out_dim,
-                     const float* w1p, const float* b1, const float* w2p, const float* b2, const float* w3p,
-                     const float* b3, float* out, const float* pre1, int32_t pre1_group,
-                     const msc_gaussian_epilogue* sample, msc_stream_t stream) {
-  if (pre1 && pre1_group < 1) return set_err(-1, "pre1_group %d must be >= 1", pre1_group);
-  // the kernel reads b1 / b2 / pre1 rows as float4
-  if (((uintptr_t)b1 | (uintptr_t)b2 | (uintptr_t)pre1 | (uintptr_t)w1p | (uintptr_t)w2p | (uintptr_t)w3p) & 15)
-    return set_err(-1, "b1, b2, pre1 and the packed weights must be 16-byte aligned");
-  if (!x || !w1p || !b1 || !w2p || !b2 || !w3p || !b3 || (!out && !sample)) return set_err(-1, "null argument");
-  if (n_rows < 0 || in_dim < 1 || in_dim > 1024 || out_dim < 1 || out_dim > 32)
-    return set_err(-1, "bad shape (n_rows %lld, in_dim %d, out_dim %d)", (long long)n_rows, in_dim, out_dim);
-  auto hs = [](int h) { return h == 64 || h == 128 || h == 256 || h == 512; };
-  if (!(hs(hidden1) && hs(hidden2)))
-    return set_err(-1, "hidden sizes %d, %d: the fused MLP supports [H1, H2] with H1, H2 in {64, 128, 256, 512}", hidden1, hidden2);
+// the plain, per-agent (mlp_multi.hip) and wide-output (mlp_wide.hip: the centralised actor, cppo.py, multi-tile MFMA
+// output layer with an LDS-staged sampling epilogue) entry points: check, sampling epilogue, launch
+static int mlp_impl(const MlpEntry& e, bool two, const MlpCall& a, const msc_gaussian_epilogue* sample, const void* sink,
+                    msc_stream_t stream) {
+  const bool wide = e.max_out > 32;
+  if (const int r = mlp_check(e, two, a, sink)) return r;
   MlpSample sm{};
-  if (const int r = mlp_sample_args(sample, out_dim, &sm)) return r;
-  HIP_TRY(launch_mlp3_relu(x, n_rows, in_dim, hidden1, hidden2, out_dim, w1p, b1, w2p, b2, w3p, b3, out, pre1,
-                           pre1 ? pre1_group : 1, (hipStream_t)stream, sample ? &sm : nullptr));
+  if (const int r = mlp_sample_args(sample, a.out_dim, !wide, e.multi ? a.group : 0, &sm)) return r;
+  const MlpSample* smp = sample ? &sm : nullptr;
+  const hipStream_t st = (hipStream_t)stream;
+  const int grp = a.pre1 ? a.group : 1;
+  if (e.multi && two)
+    HIP_TRY(launch_mlp3_relu_multi(a.x, a.n_rows / a.group, a.group, a.in_dim, a.hidden1, a.hidden2, a.out_dim, a.w1p, a.b1,
+                                   a.w2p, a.b2, a.w3p, a.b3, a.out, a.pre1, st, smp));
+  else if (e.multi)
+    HIP_TRY(launch_mlp2_relu_multi(a.x, a.n_rows / a.group, a.group, a.in_dim, a.hidden1, a.out_dim, a.w1p, a.b1, a.w3p,
+                                   a.b3, a.out, a.pre1, st, smp));
+  else if (wide && two)
+    HIP_TRY(launch_mlp3_wide(a.x, a.n_rows, a.in_dim, a.hidden1, a.hidden2, a.out_dim, a.w1p, a.b1, a.w2p, a.b2, a.w3p, a.b3,
+                             a.out, a.pre1, grp, st, smp));
+  else if (wide)
+    HIP_TRY(launch_mlp2_wide(a.x, a.n_rows, a.in_dim, a.hidden1, a.out_dim, a.w1p, a.b1, a.w3p, a.b3, a.out, a.pre1, grp, st, smp));
+  else if (two)
+    HIP_TRY(launch_mlp3_relu(a.x, a.n_rows, a.in_dim, a.hidden1, a.hidden2, a.out_dim, a.w1p, a.b1, a.w2p, a.b2, a.w3p, a.b3,
+                             a.out, a.pre1, grp, st, smp));
+  else
+    HIP_TRY(launch_mlp2_relu(a.x, a.n_rows, a.in_dim, a.hidden1, a.out_dim, a.w1p, a.b1, a.w3p, a.b3, a.out, a.pre1, grp, st, smp));
   return 0;
 }
 
@@ -1039,9 +1102,8 @@ int msc_mlp3_relu_forward(const float* x, int64_t n_rows, int32_t in_dim, int32_
                           int32_t out_dim, const float* w1p, const float* b1, const float* w2p, const float* b2,
                           const float* w3p, const float* b3, float* out, const float* pre1, int32_t pre1_group,
                           msc_stream_t stream) {
-  if (!out) return set_err(-1, "null argument");
-  return mlp3_impl(x, n_rows, in_dim, hidden1, hidden2, out_dim, w1p, b1, w2p, b2, w3p, b3, out, pre1, pre1_group,
-                   nullptr, stream);
+  return mlp_impl(MLP3, true, {x, n_rows, in_dim, hidden1, hidden2, out_dim, w1p, b1, w2p, b2, w3p, b3, out, pre1, pre1_group},
+                  nullptr, out, stream);
 }
 
 int msc_mlp3_relu_forward_sampled(const float* x, int64_t n_rows, int32_t in_dim, int32_t hidden1, int32_t hidden2,
@@ -1049,144 +1111,63 @@ int msc_mlp3_relu_forward_sampled(const float* x, int64_t n_rows, int32_t in_dim
                                   const float* b2, const float* w3p, const float* b3, float* out,
                                   const float* pre1, int32_t pre1_group, const msc_gaussian_epilogue* sample,
                                   msc_stream_t stream) {
-  if (!sample) return set_err(-1, "null argument");
-  return mlp3_impl(x, n_rows, in_dim, hidden1, hidden2, out_dim, w1p, b1, w2p, b2, w3p, b3, out, pre1, pre1_group,
-                   sample, stream);
-}
-
-static int mlp2_impl(const float* x, int64_t n_rows, int32_t in_dim, int32_t hidden, int32_t out_dim, const float* w1p,
-                     const float* b1, const float* w3p, const float* b3, float* out, const float* pre1,
-                     int32_t pre1_group, const msc_gaussian_epilogue* sample, msc_stream_t stream) {
-  if (pre1 && pre1_group < 1) return set_err(-1, "pre1_group %d must be >= 1", pre1_group);
-  if (((uintptr_t)b1 | (uintptr_t)pre1 | (uintptr_t)w1p | (uintptr_t)w3p) & 15)
-    return set_err(-1, "b1, pre1 and the packed weights must be 16-byte aligned");
-  if (!x || !w1p || !b1 || !w3p || !b3 || (!out && !sample)) return set_err(-1, "null argument");
-  if (n_rows < 0 || in_dim < 1 || in_dim > 1024 || out_dim < 1 || out_dim > 32)
-    return set_err(-1, "bad shape (n_rows %lld, in_dim %d, out_dim %d)", (long long)n_rows, in_dim, out_dim);
-  if (!mlp2_supported(hidden)) return set_err(-1, "hidden size %d: the fused MLP supports multiples of 32 up to 1024", hidden);
-  MlpSample sm{};
-  if (const int r = mlp_sample_args(sample, out_dim, &sm)) return r;
-  HIP_TRY(launch_mlp2_relu(x, n_rows, in_dim, hidden, out_dim, w1p, b1, w3p, b3, out, pre1, pre1 ? pre1_group : 1,
-                           (hipStream_t)stream, sample ? &sm : nullptr));
-  return 0;
+  return mlp_impl(MLP3, true, {x, n_rows, in_dim, hidden1, hidden2, out_dim, w1p, b1, w2p, b2, w3p, b3, out, pre1, pre1_group},
+                  sample, sample, stream);
 }
 
 int msc_mlp2_relu_forward(const float* x, int64_t n_rows, int32_t in_dim, int32_t hidden, int32_t out_dim,
                           const float* w1p, const float* b1, const float* w3p, const float* b3, float* out,
                           const float* pre1, int32_t pre1_group, msc_stream_t stream) {
-  if (!out) return set_err(-1, "null argument");
-  return mlp2_impl(x, n_rows, in_dim, hidden, out_dim, w1p, b1, w3p, b3, out, pre1, pre1_group, nullptr, stream);
+  return mlp_impl(MLP2, false, {x, n_rows, in_dim, hidden, 0, out_dim, w1p, b1, nullptr, nullptr, w3p, b3, out, pre1, pre1_group},
+                  nullptr, out, stream);
 }
 
 int msc_mlp2_relu_forward_sampled(const float* x, int64_t n_rows, int32_t in_dim, int32_t hidden, int32_t out_dim,
                                   const float* w1p, const float* b1, const float* w3p, const float* b3, float* out,
                                   const float* pre1, int32_t pre1_group, const msc_gaussian_epilogue* sample,
                                   msc_stream_t stream) {
-  if (!sample) return set_err(-1, "null argument");
-  return mlp2_impl(x, n_rows, in_dim, hidden, out_dim, w1p, b1, w3p, b3, out, pre1, pre1_group, sample, stream);
+  return mlp_impl(MLP2, false, {x, n_rows, in_dim, hidden, 0, out_dim, w1p, b1, nullptr, nullptr, w3p, b3, out, pre1, pre1_group},
+                  sample, sample, stream);
 }
 
-// per-agent policies in one launch (mlp_multi.hip): the single-policy entry points' argument checks,
-// then the multi-policy ones; hidden2 = 0 is the one-hidden-layer form
-static int mlp_multi_impl(const float* x, int64_t n_rows, int32_t n_policies, int32_t in_dim, int32_t hidden1,
-                          int32_t hidden2, int32_t out_dim, const float* w1p, const float* b1, const float* w2p,
-                          const float* b2, const float* w3p, const float* b3, float* out, const float* pre1,
-                          const msc_gaussian_epilogue* sample, msc_stream_t stream) {
-  const bool two = hidden2 != 0;
-  if (((uintptr_t)b1 | (uintptr_t)b2 | (uintptr_t)pre1 | (uintptr_t)w1p | (uintptr_t)w2p | (uintptr_t)w3p) & 15)
-    return set_err(-1, "b1, b2, pre1 and the packed weights must be 16-byte aligned");
-  if (!x || !w1p || !b1 || (two && (!w2p || !b2)) || !w3p || !b3 || (!out && !sample)) return set_err(-1, "null argument");
-  if (n_policies < 1 || n_policies > 64) return set_err(-1, "n_policies %d must be in 1..64", n_policies);
-  if (n_rows < 0 || n_rows % n_policies != 0)
-    return set_err(-1, "n_rows %lld must be a non-negative multiple of n_policies %d", (long long)n_rows, n_policies);
-  if (in_dim < 1 || in_dim > 1024 || out_dim < 1 || out_dim > 32)
-    return set_err(-1, "bad shape (n_rows %lld, in_dim %d, out_dim %d)", (long long)n_rows, in_dim, out_dim);
-  auto hs = [](int h) { return h == 64 || h == 128 || h == 256 || h == 512; };
-  if (two && !(hs(hidden1) && hs(hidden2)))
-    return set_err(-1, "hidden sizes %d, %d: the fused MLP supports [H1, H2] with H1, H2 in {64, 128, 256, 512}", hidden1, hidden2);
-  if (!two && !mlp2_supported(hidden1))
-    return set_err(-1, "hidden size %d: the fused MLP supports multiples of 32 up to 1024", hidden1);
-  MlpSample sm{};
-  if (const int r = mlp_sample_args(sample, out_dim, &sm)) return r;
-  if (sample && sample->log_std_rows != 1 && sample->log_std_rows != n_policies)
-    return set_err(-1, "log_std_rows %d must be 1 or n_policies %d", sample->log_std_rows, n_policies);
-  const int64_t E = n_rows / n_policies;
-  if (((E + 31) / 32 + 3) / 4 * n_policies > 0x7fffffff) return set_err(-1, "n_rows %lld: too many rows for one launch", (long long)n_rows);
-  if (two)
-    HIP_TRY(launch_mlp3_relu_multi(x, E, n_policies, in_dim, hidden1, hidden2, out_dim, w1p, b1, w2p, b2, w3p, b3, out,
-                                   pre1, (hipStream_t)stream, sample ? &sm : nullptr));
-  else
-    HIP_TRY(launch_mlp2_relu_multi(x, E, n_policies, in_dim, hidden1, out_dim, w1p, b1, w3p, b3, out, pre1,
-                                   (hipStream_t)stream, sample ? &sm : nullptr));
-  return 0;
-}
-
+// hidden2 = 0 is the one-hidden-layer form, reached through the msc_mlp2_* entry point
 int msc_mlp3_relu_multi(const float* x, int64_t n_rows, int32_t n_policies, int32_t in_dim, int32_t hidden1,
                         int32_t hidden2, int32_t out_dim, const float* w1p, const float* b1, const float* w2p,
                         const float* b2, const float* w3p, const float* b3, float* out, const float* pre1,
                         const msc_gaussian_epilogue* sample, msc_stream_t stream) {
-  if (hidden2 == 0) return set_err(-1, "hidden2 must be one of {64, 128, 256, 512} (one hidden layer: msc_mlp2_relu_multi)");
-  return mlp_multi_impl(x, n_rows, n_policies, in_dim, hidden1, hidden2, out_dim, w1p, b1, w2p, b2, w3p, b3, out, pre1,
-                        sample, stream);
+  return mlp_impl(MLP_MULTI3, hidden2 != 0,
+                  {x, n_rows, in_dim, hidden1, hidden2, out_dim, w1p, b1, w2p, b2, w3p, b3, out, pre1, n_policies}, sample,
+                  out ? (const void*)out : sample, stream);
 }
 
 int msc_mlp2_relu_multi(const float* x, int64_t n_rows, int32_t n_policies, int32_t in_dim, int32_t hidden,
                         int32_t out_dim, const float* w1p, const float* b1, const float* w3p, const float* b3, float* out,
                         const float* pre1, const msc_gaussian_epilogue* sample, msc_stream_t stream) {
-  return mlp_multi_impl(x, n_rows, n_policies, in_dim, hidden, 0, out_dim, w1p, b1, nullptr, nullptr, w3p, b3, out, pre1,
-                        sample, stream);
+  return mlp_impl(MLP_MULTI2, false,
+                  {x, n_rows, in_dim, hidden, 0, out_dim, w1p, b1, nullptr, nullptr, w3p, b3, out, pre1, n_policies}, sample,
+                  out ? (const void*)out : sample, stream);
 }
 
-// wide-output MLPs (the centralised actor, cppo.py: MLPArchitecture.build over the global observation
-// to the joint action): multi-tile MFMA output layer, optional LDS-staged sampling epilogue
 int msc_mlp_wide_supported(int32_t hidden1, int32_t hidden2, int32_t out_dim) {
   return mlp_wide_supported(hidden1, hidden2, out_dim) ? 1 : 0;
-}
-
-static int mlp_wide_impl(const float* x, int64_t n_rows, int32_t in_dim, int32_t hidden1, int32_t hidden2,
-                         int32_t out_dim, const float* w1p, const float* b1, const float* w2p, const float* b2,
-                         const float* w3p, const float* b3, float* out, const float* pre1, int32_t pre1_group,
-                         const msc_gaussian_epilogue* g, msc_stream_t stream) {
-  const bool two = hidden2 != 0;
-  if (pre1 && pre1_group < 1) return set_err(-1, "pre1_group %d must be >= 1", pre1_group);
-  if (((uintptr_t)b1 | (uintptr_t)b2 | (uintptr_t)pre1 | (uintptr_t)w1p | (uintptr_t)w2p | (uintptr_t)w3p) & 15)
-    return set_err(-1, "b1, b2, pre1 and the packed weights must be 16-byte aligned");
-  if (!x || !w1p || !b1 || (two && (!w2p || !b2)) || !w3p || !b3 || (!out && !g)) return set_err(-1, "null argument");
-  if (n_rows < 0 || in_dim < 1 || in_dim > 1024 || out_dim < 1 || out_dim > 128)
-    return set_err(-1, "bad shape (n_rows %lld, in_dim %d, out_dim %d)", (long long)n_rows, in_dim, out_dim);
-  if (!mlp_wide_supported(hidden1, hidden2, out_dim))
-    return two ? set_err(-1, "hidden sizes %d, %d: the wide MLP supports [H1, H2] with H1, H2 in {64, 128, 256, 512}", hidden1, hidden2)
-               : set_err(-1, "hidden size %d: the wide MLP supports multiples of 32 up to 1024", hidden1);
-  MlpSample sm{};
-  if (g) {
-    if (!g->log_std || !g->eps || !g->actions || !g->logp || !g->clipped) return set_err(-1, "null sampling buffer");
-    if (g->log_std_rows < 1) return set_err(-1, "log_std_rows %d must be >= 1", g->log_std_rows);
-    sm = MlpSample{g->log_std, g->log_std_rows, g->logstd_floor, g->eps, g->actions, g->logp, g->clipped};
-  }
-  if (two)
-    HIP_TRY(launch_mlp3_wide(x, n_rows, in_dim, hidden1, hidden2, out_dim, w1p, b1, w2p, b2, w3p, b3, out, pre1,
-                             pre1 ? pre1_group : 1, (hipStream_t)stream, g ? &sm : nullptr));
-  else
-    HIP_TRY(launch_mlp2_wide(x, n_rows, in_dim, hidden1, out_dim, w1p, b1, w3p, b3, out, pre1, pre1 ? pre1_group : 1,
-                             (hipStream_t)stream, g ? &sm : nullptr));
-  return 0;
 }
 
 int msc_mlp3_relu_wide(const float* x, int64_t n_rows, int32_t in_dim, int32_t hidden1, int32_t hidden2,
                        int32_t out_dim, const float* w1p, const float* b1, const float* w2p, const float* b2,
                        const float* w3p, const float* b3, float* out, const float* pre1, int32_t pre1_group,
                        const msc_gaussian_epilogue* sample, msc_stream_t stream) {
-  if (hidden2 == 0) return set_err(-1, "hidden2 must be one of {64, 128, 256, 512} (one hidden layer: msc_mlp2_relu_wide)");
-  return mlp_wide_impl(x, n_rows, in_dim, hidden1, hidden2, out_dim, w1p, b1, w2p, b2, w3p, b3, out, pre1, pre1_group,
-                       sample, stream);
+  return mlp_impl(MLP_WIDE3, hidden2 != 0,
+                  {x, n_rows, in_dim, hidden1, hidden2, out_dim, w1p, b1, w2p, b2, w3p, b3, out, pre1, pre1_group}, sample,
+                  out ? (const void*)out : sample, stream);
 }
 
 int msc_mlp2_relu_wide(const float* x, int64_t n_rows, int32_t in_dim, int32_t hidden, int32_t out_dim,
                        const float* w1p, const float* b1, const float* w3p, const float* b3, float* out,
                        const float* pre1, int32_t pre1_group, const msc_gaussian_epilogue* sample,
                        msc_stream_t stream) {
-  return mlp_wide_impl(x, n_rows, in_dim, hidden, 0, out_dim, w1p, b1, nullptr, nullptr, w3p, b3, out, pre1, pre1_group,
-                       sample, stream);
+  return mlp_impl(MLP_WIDE2, false,
+                  {x, n_rows, in_dim, hidden, 0, out_dim, w1p, b1, nullptr, nullptr, w3p, b3, out, pre1, pre1_group}, sample,
+                  out ? (const void*)out : sample, stream);
 }
 
 // replaces the centralised wrapper's sum(rewards.values()) (src/environment/envs/single_env.py:156)
@@ -1239,12 +1220,9 @@ int msc_mlp3_relu_musigma(const float* x, int64_t n_rows, int32_t in_dim, int32_
                           const float* w1p, const float* b1, const float* w2p, const float* b2, const float* whp,
                           const float* bh, const float* pre1, int32_t pre1_group, const msc_musigma_epilogue* head,
                           msc_stream_t stream) {
-  if (pre1 && pre1_group < 1) return set_err(-1, "pre1_group %d must be >= 1", pre1_group);
-  if (((uintptr_t)b1 | (uintptr_t)b2 | (uintptr_t)pre1 | (uintptr_t)w1p | (uintptr_t)w2p | (uintptr_t)whp) & 15)
-    return set_err(-1, "b1, b2, pre1 and the packed weights must be 16-byte aligned");
-  if (!x || !w1p || !b1 || !w2p || !b2 || !whp || !bh) return set_err(-1, "null argument");
-  if (n_rows < 0 || in_dim < 1 || in_dim > 1024) return set_err(-1, "bad shape (n_rows %lld, in_dim %d)", (long long)n_rows, in_dim);
-  if (hidden2 == 0) return set_err(-1, "hidden2 must be one of {64, 128, 256, 512} (one hidden layer: msc_mlp2_relu_musigma)");
+  if (const int r = mlp_check(MLP_HEAD3, true, {x, n_rows, in_dim, hidden1, hidden2, 0, w1p, b1, w2p, b2, whp, bh, nullptr,
+                                                pre1, pre1_group}, head))
+    return r;
   MlpMuSigma ep{};
   if (const int r = musigma_args(head, hidden1, hidden2, k, &ep)) return r;
   HIP_TRY(launch_mlp3_musigma(x, n_rows, in_dim, hidden1, hidden2, k, w1p, b1, w2p, b2, whp, bh, pre1,
@@ -1255,16 +1233,35 @@ int msc_mlp3_relu_musigma(const float* x, int64_t n_rows, int32_t in_dim, int32_
 int msc_mlp2_relu_musigma(const float* x, int64_t n_rows, int32_t in_dim, int32_t hidden, int32_t k, const float* w1p,
                           const float* b1, const float* whp, const float* bh, const float* pre1, int32_t pre1_group,
                           const msc_musigma_epilogue* head, msc_stream_t stream) {
-  if (pre1 && pre1_group < 1) return set_err(-1, "pre1_group %d must be >= 1", pre1_group);
-  if (((uintptr_t)b1 | (uintptr_t)pre1 | (uintptr_t)w1p | (uintptr_t)whp) & 15)
-    return set_err(-1, "b1, pre1 and the packed weights must be 16-byte aligned");
-  if (!x || !w1p || !b1 || !whp || !bh) return set_err(-1, "null argument");
-  if (n_rows < 0 || in_dim < 1 || in_dim > 1024) return set_err(-1, "bad shape (n_rows %lld, in_dim %d)", (long long)n_rows, in_dim);
+  if (const int r = mlp_check(MLP_HEAD2, false, {x, n_rows, in_dim, hidden, 0, 0, w1p, b1, nullptr, nullptr, whp, bh, nullptr,
+                                                 pre1, pre1_group}, head))
+    return r;
   MlpMuSigma ep{};
   if (const int r = musigma_args(head, hidden, 0, k, &ep)) return r;
   HIP_TRY(launch_mlp2_musigma(x, n_rows, in_dim, hidden, k, w1p, b1, whp, bh, pre1, pre1 ? pre1_group : 1,
                               (hipStream_t)stream, ep));
   return 0;
+}
+
+// what the launchers would pick, through their own dispatch with a recording callable (mlp_dispatch.hpp)
+int msc_mlp_plan(int32_t family, int32_t hidden1, int32_t hidden2, int32_t out_dim, int64_t n_rows, int32_t n_policies,
+                 int32_t* out, int32_t n) {
+  if (!out && n > 0) return set_err(-1, "null argument");
+  if (family < MSC_MLP_RELU || family > MSC_MLP_WIDE) return set_err(-1, "family %d: must be MSC_MLP_* (0..3)", family);
+  const int np = family == MSC_MLP_MULTI ? n_policies : 1;
+  if (np < 1 || np > 64) return set_err(-1, "n_policies %d must be in 1..64", np);
+  if (n_rows < 0 || n_rows % np != 0)
+    return set_err(-1, "n_rows %lld must be a non-negative multiple of n_policies %d", (long long)n_rows, np);
+  MlpPlan p{};
+  const bool ok = family == MSC_MLP_MUSIGMA ? mlp_musigma_plan(hidden1, hidden2, out_dim, n_rows, &p)
+                  : family == MSC_MLP_WIDE  ? mlp_wide_plan(hidden1, hidden2, out_dim, n_rows, &p)
+                                            : mlp_relu_plan(hidden1, hidden2, out_dim, n_rows / np,
+                                                            family == MSC_MLP_MULTI ? np : 0, &p);
+  if (!ok) p = MlpPlan{};
+  const int32_t v[MSC_MLP_PLAN_N] = {ok, p.nt1, p.nt2, p.p, p.wpe, p.il, p.width, p.tb, (int32_t)p.lds, (int32_t)p.grid};
+  const int m = n < MSC_MLP_PLAN_N ? n : MSC_MLP_PLAN_N;
+  for (int i = 0; i < m; i++) out[i] = v[i];
+  return m;
 }
 
 // GRU networks (replaces GRUArchitecture's gru -> output_proj as BaseRLModule._forward_gru steps it,

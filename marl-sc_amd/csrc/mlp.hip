@@ -23,7 +23,7 @@
 #include <stdlib.h>
 
 #include "env.hpp"
-#include "mlp_kernels.hpp"  // mlp3_relu_kernel, mlp2_relu_kernel, sample_row
+#include "mlp_relu_launch.hpp"  // the launchers over MULTI, instantiated here with MULTI = false
 
 namespace msc {
 
@@ -61,127 +61,32 @@ int mlp3_valu_outputs(int KO) {
 hipError_t launch_mlp3_relu(const float* x, int64_t n, int L, int H1, int H2, int KO, const float* w1p, const float* b1,
                             const float* w2p, const float* b2, const float* w3p, const float* b3, float* out,
                             const float* pre1, int grp, hipStream_t st, const MlpSample* smp) {
-  if (n == 0) return hipSuccess;
-  const MlpSample sm = smp ? *smp : MlpSample{};
-  if (sm.act && mlp3_valu_outputs(KO) == 0) return hipErrorInvalidValue;  // sampling needs the VALU output layer
-  const int KS1 = (L + 1) / 2;
-  const int64_t tiles = (n + 31) / 32;
-  const dim3 grid((unsigned)((tiles + 3) / 4)), block(256);
-  const float4* w1 = reinterpret_cast<const float4*>(w1p);
-  const float4* w2 = reinterpret_cast<const float4*>(w2p);
-  const float4* w3 = reinterpret_cast<const float4*>(w3p);
-#define MSC_MLP_LAUNCH_IL(NT1, NT2, P, WPE, VKO, IL)                                                                   \
-  hipLaunchKernelGGL((mlp3_relu_kernel<NT1, NT2, P, WPE, VKO, IL>), grid, block, 0, st, x, n, L, KS1, w1, b1, w2, b2,   \
-                     w3, b3, KO, out, pre1, grp, mlp_prio(), sm)
-#define MSC_MLP_LAUNCH(NT1, NT2, P, WPE, VKO) MSC_MLP_LAUNCH_IL(NT1, NT2, P, WPE, VKO, false)
-  // the output layer on the VALU for KO <= 8 (VKO = 1, 2, 4, 5 or 8: the next supported count >= KO)
-  const int vko = mlp3_valu_outputs(KO);
-#define MSC_MLP_VKO(NT1, NT2, P, WPE)                                 \
-  switch (vko) {                                                      \
-    case 1: MSC_MLP_LAUNCH(NT1, NT2, P, WPE, 1); break;               \
-    case 2: MSC_MLP_LAUNCH(NT1, NT2, P, WPE, 2); break;               \
-    case 4: MSC_MLP_LAUNCH(NT1, NT2, P, WPE, 4); break;               \
-    case 5: MSC_MLP_LAUNCH(NT1, NT2, P, WPE, 5); break;               \
-    case 8: MSC_MLP_LAUNCH(NT1, NT2, P, WPE, 8); break;               \
-    default: MSC_MLP_LAUNCH(NT1, NT2, P, WPE, 0); break;              \
-  }
-#define MSC_MLP_VKO_IL(NT1, NT2, P, WPE)                                 \
-  switch (vko) {                                                         \
-    case 1: MSC_MLP_LAUNCH_IL(NT1, NT2, P, WPE, 1, true); break;         \
-    case 2: MSC_MLP_LAUNCH_IL(NT1, NT2, P, WPE, 2, true); break;         \
-    case 4: MSC_MLP_LAUNCH_IL(NT1, NT2, P, WPE, 4, true); break;         \
-    case 5: MSC_MLP_LAUNCH_IL(NT1, NT2, P, WPE, 5, true); break;         \
-    case 8: MSC_MLP_LAUNCH_IL(NT1, NT2, P, WPE, 8, true); break;         \
-    default: MSC_MLP_LAUNCH(NT1, NT2, P, WPE, 0); break;                 \
-  }
-  // H1 held whole in registers, H2 in passes of P tiles; (NT1, P) sets the register budget
-  // (16 NT1 + 24 P + ~48 per lane) and with it the waves per SIMD
-  if (H1 == 256 && H2 == 256) {
-    if (mlp_p8() == 41) MSC_MLP_VKO_IL(8, 8, 4, 1)
-    else if (mlp_p8() == 21) MSC_MLP_VKO_IL(8, 8, 2, 1)
-    else if (mlp_p8() == 8) MSC_MLP_VKO(8, 8, 8, 1)
-    else if (mlp_p8() == 4) MSC_MLP_VKO(8, 8, 4, 2)
-    else MSC_MLP_VKO(8, 8, 2, 2)
-  } else if (H1 == 128 && H2 == 128) {
-    MSC_MLP_VKO(4, 4, 4, 2)
-  } else if (H1 == 64 && H2 == 64) {
-    MSC_MLP_VKO(2, 2, 2, 4)
-  } else if (H1 == 64 && H2 == 128) {
-    MSC_MLP_VKO(2, 4, 2, 4)
-  } else if (H1 == 64 && H2 == 256) {
-    MSC_MLP_VKO(2, 8, 2, 4)
-  } else if (H1 == 64 && H2 == 512) {
-    MSC_MLP_VKO(2, 16, 2, 4)
-  } else if (H1 == 128 && H2 == 64) {
-    MSC_MLP_VKO(4, 2, 2, 2)
-  } else if (H1 == 128 && H2 == 256) {
-    MSC_MLP_VKO(4, 8, 4, 2)
-  } else if (H1 == 128 && H2 == 512) {
-    MSC_MLP_VKO(4, 16, 4, 2)
-  } else if (H1 == 256 && H2 == 64) {
-    MSC_MLP_VKO(8, 2, 2, 2)
-  } else if (H1 == 256 && H2 == 128) {
-    MSC_MLP_VKO(8, 4, 4, 2)
-  } else if (H1 == 256 && H2 == 512) {
-    MSC_MLP_VKO(8, 16, 8, 1)
-  } else if (H1 == 512 && H2 == 64) {
-    MSC_MLP_VKO(16, 2, 2, 1)
-  } else if (H1 == 512 && H2 == 128) {
-    MSC_MLP_VKO(16, 4, 4, 1)
-  } else if (H1 == 512 && H2 == 256) {
-    MSC_MLP_VKO(16, 8, 4, 1)
-  } else if (H1 == 512 && H2 == 512) {
-    MSC_MLP_VKO(16, 16, 4, 1)
-  } else {
-    return hipErrorInvalidValue;
-  }
-#undef MSC_MLP_VKO
-#undef MSC_MLP_VKO_IL
-#undef MSC_MLP_LAUNCH_IL
-#undef MSC_MLP_LAUNCH
-  return hipGetLastError();
+  return launch_mlp3_relu_t<false>(x, n, grp, L, H1, H2, KO, w1p, b1, w2p, b2, w3p, b3, out, pre1, st, smp);
 }
 
-// one hidden layer of H1 = 32 NT1 units (NT1 <= 32): TB tiles per group, the largest power of two
-// <= 8 dividing NT1
+// one hidden layer of H1 = 32 NT1 units (NT1 <= 32)
 bool mlp2_supported(int H1) { return H1 >= 32 && H1 <= 1024 && H1 % 32 == 0; }
 
 hipError_t launch_mlp2_relu(const float* x, int64_t n, int L, int H1, int KO, const float* w1p, const float* b1,
                             const float* w3p, const float* b3, float* out, const float* pre1, int grp, hipStream_t st,
                             const MlpSample* smp) {
-  if (n == 0) return hipSuccess;
-  if (!mlp2_supported(H1)) return hipErrorInvalidValue;
-  const MlpSample sm = smp ? *smp : MlpSample{};
-  if (sm.act && mlp3_valu_outputs(KO) == 0) return hipErrorInvalidValue;
-  const int KS1 = (L + 1) / 2, NT1 = H1 / 32;
-  const int TB = NT1 % 8 == 0 ? 8 : NT1 % 4 == 0 ? 4 : NT1 % 2 == 0 ? 2 : 1;
-  const int64_t tiles = (n + 31) / 32;
-  const dim3 grid((unsigned)((tiles + 3) / 4)), block(256);
-  const float4* w1 = reinterpret_cast<const float4*>(w1p);
-  const float4* w3 = reinterpret_cast<const float4*>(w3p);
-  const int vko = mlp3_valu_outputs(KO);
-  const size_t lds = vko > 0 ? (size_t)NT1 * 16 * 2 * 2 * sizeof(float4) : 0;
-#define MSC_MLP2_LAUNCH(TBV, WPE, VKO)                                                                              \
-  hipLaunchKernelGGL((mlp2_relu_kernel<TBV, WPE, VKO>), grid, block, lds, st, x, n, L, KS1, NT1, w1, b1, w3, b3, KO, \
-                     out, pre1, grp, mlp_prio(), sm)
-#define MSC_MLP2_VKO(TBV, WPE)                  \
-  switch (vko) {                                \
-    case 1: MSC_MLP2_LAUNCH(TBV, WPE, 1); break; \
-    case 2: MSC_MLP2_LAUNCH(TBV, WPE, 2); break; \
-    case 4: MSC_MLP2_LAUNCH(TBV, WPE, 4); break; \
-    case 5: MSC_MLP2_LAUNCH(TBV, WPE, 5); break; \
-    case 8: MSC_MLP2_LAUNCH(TBV, WPE, 8); break; \
-    default: MSC_MLP2_LAUNCH(TBV, WPE, 0); break; \
-  }
-  switch (TB) {
-    case 8: MSC_MLP2_VKO(8, 2) break;
-    case 4: MSC_MLP2_VKO(4, 4) break;
-    case 2: MSC_MLP2_VKO(2, 4) break;
-    default: MSC_MLP2_VKO(1, 4) break;
-  }
-#undef MSC_MLP2_VKO
-#undef MSC_MLP2_LAUNCH
-  return hipGetLastError();
+  return launch_mlp2_relu_t<false>(x, n, grp, L, H1, KO, w1p, b1, w3p, b3, out, pre1, st, smp);
+}
+
+// what the launchers above (NP = 0) or mlp_multi.hip's (NP policies of `rows` rows each) would pick
+bool mlp_relu_plan(int H1, int H2, int KO, int64_t rows, int NP, MlpPlan* p) {
+  const MlpGeom g = mlp_geom(rows, 0, NP);
+  *p = MlpPlan{};
+  p->grid = g.grid;
+  if (!g.ok) return false;
+  if (H2 != 0)
+    return mlp3_relu_choose(H1, H2, KO, [&](auto form, auto vko, auto il) {
+      using Fm = decltype(form);
+      p->nt1 = Fm::nt1, p->nt2 = Fm::nt2, p->p = Fm::p, p->wpe = Fm::wpe, p->il = il, p->width = vko;
+    });
+  return mlp2_relu_choose(H1, KO, [&](auto tb, auto vko, size_t lds) {
+    p->nt1 = H1 / 32, p->tb = tb, p->wpe = mlp2_relu_wpe(tb), p->width = vko, p->lds = (int64_t)lds;
+  });
 }
 
 }  // namespace msc

@@ -1,6 +1,7 @@
 // The fused policy-MLP kernel templates (see mlp.hip for the design): shared by mlp.hip (plain output
-// layer, optional sampling epilogue) and mlp_musigma.hip (dual mu / sigma head), which instantiate
-// them in separate translation units so that they compile in parallel.
+// layer, optional sampling epilogue), mlp_multi.hip (the same for per-agent policies) and mlp_musigma.hip
+// (dual mu / sigma head), which instantiate them in separate translation units so that they compile in
+// parallel. Which instantiation a launch takes is decided in one place, mlp_dispatch.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

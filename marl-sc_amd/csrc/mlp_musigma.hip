@@ -6,13 +6,13 @@
 // The backbone ends in a Linear with no activation and the two heads are Linear, so the host folds
 // that Linear into the heads (marlsc/mlp.py:fold_head, f64, rounded once): the kernel sees the
 // hidden layers of a plain actor and a 2 K-row output layer, which it runs on the VALU as 2 x VKO
-// per-lane sums (K <= 8). This translation unit only instantiates the dual-head forms, beside
-// mlp.hip's, so that the two compile in parallel; per-head widths 2, 4, 5 and 8 (K = 1 runs as 2,
-// 3 as 4, 6 and 7 as 8).
+// per-lane sums (K <= 8). This translation unit only instantiates the dual-head forms (EP = MlpMuSigma)
+// of the form table in mlp_dispatch.hpp, beside mlp.hip's, so that the two compile in parallel; per-head
+// widths 2, 4, 5 and 8 (K = 1 runs as 2, 3 as 4, 6 and 7 as 8).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "env.hpp"
+#include "mlp_dispatch.hpp"
 #include "mlp_kernels.hpp"
 
 namespace msc {
@@ -25,72 +25,8 @@ int mlp_head_width(int K) {
 // [256, 256]: the interleaved forms (MSC_MLP_P8 = 41, 21) and the one-pass form (8); the losing A/B
 // forms (4, 2: two waves per SIMD, spills) have no dual-head variant
 bool mlp3_head_supported(int H1, int H2) {
-  auto hs = [](int v) { return v == 64 || v == 128 || v == 256 || v == 512; };
-  if (!hs(H1) || !hs(H2)) return false;
+  if (!mlp_hidden_ok(H1) || !mlp_hidden_ok(H2)) return false;
   return !(H1 == 256 && H2 == 256 && (mlp_p8() == 4 || mlp_p8() == 2));
-}
-
-hipError_t launch_mlp3_musigma(const float* x, int64_t n, int L, int H1, int H2, int K, const float* w1p, const float* b1,
-                               const float* w2p, const float* b2, const float* whp, const float* bh, const float* pre1,
-                               int grp, hipStream_t st, const MlpMuSigma& ep) {
-  if (n == 0) return hipSuccess;
-  const int vk = mlp_head_width(K);
-  if (vk == 0 || !mlp3_head_supported(H1, H2)) return hipErrorInvalidValue;
-  const int KS1 = (L + 1) / 2;
-  const int64_t tiles = (n + 31) / 32;
-  const dim3 grid((unsigned)((tiles + 3) / 4)), block(256);
-  const float4* w1 = reinterpret_cast<const float4*>(w1p);
-  const float4* w2 = reinterpret_cast<const float4*>(w2p);
-  const float4* wh = reinterpret_cast<const float4*>(whp);
-#define MSC_HEAD_LAUNCH(NT1, NT2, P, WPE, VK, IL)                                                                   \
-  hipLaunchKernelGGL((mlp3_relu_kernel<NT1, NT2, P, WPE, VK, IL, MlpMuSigma>), grid, block, 0, st, x, n, L, KS1, w1, \
-                     b1, w2, b2, wh, bh, K, nullptr, pre1, grp, mlp_prio(), ep)
-#define MSC_HEAD_VK(NT1, NT2, P, WPE, IL)                      \
-  switch (vk) {                                                \
-    case 2: MSC_HEAD_LAUNCH(NT1, NT2, P, WPE, 2, IL); break;   \
-    case 4: MSC_HEAD_LAUNCH(NT1, NT2, P, WPE, 4, IL); break;   \
-    case 5: MSC_HEAD_LAUNCH(NT1, NT2, P, WPE, 5, IL); break;   \
-    default: MSC_HEAD_LAUNCH(NT1, NT2, P, WPE, 8, IL); break;  \
-  }
-  // the tile shapes of launch_mlp3_relu (mlp.hip)
-  if (H1 == 256 && H2 == 256) {
-    if (mlp_p8() == 41) MSC_HEAD_VK(8, 8, 4, 1, true)
-    else if (mlp_p8() == 21) MSC_HEAD_VK(8, 8, 2, 1, true)
-    else MSC_HEAD_VK(8, 8, 8, 1, false)
-  } else if (H1 == 128 && H2 == 128) {
-    MSC_HEAD_VK(4, 4, 4, 2, false)
-  } else if (H1 == 64 && H2 == 64) {
-    MSC_HEAD_VK(2, 2, 2, 4, false)
-  } else if (H1 == 64 && H2 == 128) {
-    MSC_HEAD_VK(2, 4, 2, 4, false)
-  } else if (H1 == 64 && H2 == 256) {
-    MSC_HEAD_VK(2, 8, 2, 4, false)
-  } else if (H1 == 64 && H2 == 512) {
-    MSC_HEAD_VK(2, 16, 2, 4, false)
-  } else if (H1 == 128 && H2 == 64) {
-    MSC_HEAD_VK(4, 2, 2, 2, false)
-  } else if (H1 == 128 && H2 == 256) {
-    MSC_HEAD_VK(4, 8, 4, 2, false)
-  } else if (H1 == 128 && H2 == 512) {
-    MSC_HEAD_VK(4, 16, 4, 2, false)
-  } else if (H1 == 256 && H2 == 64) {
-    MSC_HEAD_VK(8, 2, 2, 2, false)
-  } else if (H1 == 256 && H2 == 128) {
-    MSC_HEAD_VK(8, 4, 4, 2, false)
-  } else if (H1 == 256 && H2 == 512) {
-    MSC_HEAD_VK(8, 16, 8, 1, false)
-  } else if (H1 == 512 && H2 == 64) {
-    MSC_HEAD_VK(16, 2, 2, 1, false)
-  } else if (H1 == 512 && H2 == 128) {
-    MSC_HEAD_VK(16, 4, 4, 1, false)
-  } else if (H1 == 512 && H2 == 256) {
-    MSC_HEAD_VK(16, 8, 4, 1, false)
-  } else {
-    MSC_HEAD_VK(16, 16, 4, 1, false)
-  }
-#undef MSC_HEAD_VK
-#undef MSC_HEAD_LAUNCH
-  return hipGetLastError();
 }
 
 // one hidden layer: the staged head weights (H1 x stride floats) must fit the 32 KiB the single-head
@@ -99,38 +35,64 @@ bool mlp2_head_supported(int H1, int width) {
   return mlp2_supported(H1) && width > 0 && (size_t)H1 * mlp_head_stride(width) * sizeof(float) <= 32768;
 }
 
+// f(form, VK): mlp3_relu_kernel's instantiation for hidden sizes [H1, H2] and K actions per head
+template <class F>
+static bool head3_choose(int H1, int H2, int K, F&& f) {
+  const int vk = mlp_head_width(K);
+  if (vk == 0 || !mlp3_head_supported(H1, H2)) return false;
+  return mlp3_relu_form<false>(H1, H2, mlp_p8(),
+                               [&](auto form) { dispatch_int_or<8, 2, 4, 5>(vk, [&](auto v) { f(form, v); }); });
+}
+
+// f(TB, VK, dynamic LDS bytes): mlp2_relu_kernel's, which stages the head weights in LDS
+template <class F>
+static bool head2_choose(int H1, int K, F&& f) {
+  const int vk = mlp_head_width(K);
+  if (!mlp2_head_supported(H1, vk)) return false;
+  const size_t lds = (size_t)H1 * mlp_head_stride(vk) * sizeof(float);
+  mlp2_form(H1 / 32, true, [&](auto tb) { dispatch_int_or<8, 2, 4, 5>(vk, [&](auto v) { f(tb, v, lds); }); });
+  return true;
+}
+
+hipError_t launch_mlp3_musigma(const float* x, int64_t n, int L, int H1, int H2, int K, const float* w1p, const float* b1,
+                               const float* w2p, const float* b2, const float* whp, const float* bh, const float* pre1,
+                               int grp, hipStream_t st, const MlpMuSigma& ep) {
+  if (n == 0) return hipSuccess;
+  const MlpGeom g = mlp_geom(n, L);
+  const bool found = head3_choose(H1, H2, K, [&](auto form, auto vk) {
+    using Fm = decltype(form);
+    hipLaunchKernelGGL((mlp3_relu_kernel<Fm::nt1, Fm::nt2, Fm::p, Fm::wpe, decltype(vk)::value, Fm::il, MlpMuSigma>),
+                       dim3(g.grid), dim3(256), 0, st, x, n, L, g.KS1, mlp_f4(w1p), b1, mlp_f4(w2p), b2, mlp_f4(whp), bh,
+                       K, nullptr, pre1, grp, g.prio, ep);
+  });
+  return found ? hipGetLastError() : hipErrorInvalidValue;
+}
+
 hipError_t launch_mlp2_musigma(const float* x, int64_t n, int L, int H1, int K, const float* w1p, const float* b1,
                                const float* whp, const float* bh, const float* pre1, int grp, hipStream_t st,
                                const MlpMuSigma& ep) {
   if (n == 0) return hipSuccess;
-  const int vk = mlp_head_width(K);
-  if (!mlp2_head_supported(H1, vk)) return hipErrorInvalidValue;
-  const int KS1 = (L + 1) / 2, NT1 = H1 / 32;
-  const int TB = NT1 % 8 == 0 ? 8 : NT1 % 4 == 0 ? 4 : NT1 % 2 == 0 ? 2 : 1;
-  const int64_t tiles = (n + 31) / 32;
-  const dim3 grid((unsigned)((tiles + 3) / 4)), block(256);
-  const float4* w1 = reinterpret_cast<const float4*>(w1p);
-  const float4* wh = reinterpret_cast<const float4*>(whp);
-  const size_t lds = (size_t)H1 * mlp_head_stride(vk) * sizeof(float);
-#define MSC_HEAD2_LAUNCH(TBV, WPE, VK)                                                                             \
-  hipLaunchKernelGGL((mlp2_relu_kernel<TBV, WPE, VK, MlpMuSigma>), grid, block, lds, st, x, n, L, KS1, NT1, w1, b1, \
-                     wh, bh, K, nullptr, pre1, grp, mlp_prio(), ep)
-#define MSC_HEAD2_VK(TBV, WPE)                         \
-  switch (vk) {                                        \
-    case 2: MSC_HEAD2_LAUNCH(TBV, WPE, 2); break;      \
-    case 4: MSC_HEAD2_LAUNCH(TBV, WPE, 4); break;      \
-    case 5: MSC_HEAD2_LAUNCH(TBV, WPE, 5); break;      \
-    default: MSC_HEAD2_LAUNCH(TBV, WPE, 8); break;     \
-  }
-  switch (TB) {
-    case 8: MSC_HEAD2_VK(8, 2) break;
-    case 4: MSC_HEAD2_VK(4, 4) break;
-    case 2: MSC_HEAD2_VK(2, 4) break;
-    default: MSC_HEAD2_VK(1, 4) break;
-  }
-#undef MSC_HEAD2_VK
-#undef MSC_HEAD2_LAUNCH
-  return hipGetLastError();
+  const MlpGeom g = mlp_geom(n, L);
+  const bool found = head2_choose(H1, K, [&](auto tb, auto vk, size_t lds) {
+    constexpr int TB = decltype(tb)::value;
+    hipLaunchKernelGGL((mlp2_relu_kernel<TB, mlp2_relu_wpe(TB), decltype(vk)::value, MlpMuSigma>), dim3(g.grid),
+                       dim3(256), lds, st, x, n, L, g.KS1, H1 / 32, mlp_f4(w1p), b1, mlp_f4(whp), bh, K, nullptr, pre1,
+                       grp, g.prio, ep);
+  });
+  return found ? hipGetLastError() : hipErrorInvalidValue;
+}
+
+bool mlp_musigma_plan(int H1, int H2, int K, int64_t rows, MlpPlan* p) {
+  *p = MlpPlan{};
+  p->grid = mlp_geom(rows, 0).grid;
+  if (H2 != 0)
+    return head3_choose(H1, H2, K, [&](auto form, auto vk) {
+      using Fm = decltype(form);
+      p->nt1 = Fm::nt1, p->nt2 = Fm::nt2, p->p = Fm::p, p->wpe = Fm::wpe, p->il = Fm::il, p->width = vk;
+    });
+  return head2_choose(H1, K, [&](auto tb, auto vk, size_t lds) {
+    p->nt1 = H1 / 32, p->tb = tb, p->wpe = mlp2_relu_wpe(tb), p->width = vk, p->lds = (int64_t)lds;
+  });
 }
 
 }  // namespace msc

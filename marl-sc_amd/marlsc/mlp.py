@@ -102,6 +102,23 @@ def w3_layout(out_dim: int) -> int:
     return v
 
 
+PLAN_FAMILIES = {"relu": 0, "multi": 1, "musigma": 2, "wide": 3}  # MSC_MLP_*
+# msc_mlp_plan's list (include/marlsc.h)
+PLAN_KEYS = ("supported", "nt1", "nt2", "p", "wpe", "il", "width", "tb", "lds_bytes", "grid_blocks")
+
+
+def plan(family: str, hidden1: int, hidden2: int, out_dim: int, n_rows: int, n_policies: int = 1) -> Dict[str, int]:
+    """The kernel instantiation and launch geometry a family's entry points would pick under the current
+    knobs (msc_mlp_plan): host code only, no GPU is touched. hidden2 = 0: one hidden layer; out_dim: k for
+    "musigma"; n_policies: "multi" only."""
+    buf = (C.c_int32 * len(PLAN_KEYS))()
+    n = abi.lib().msc_mlp_plan(PLAN_FAMILIES[family], int(hidden1), int(hidden2), int(out_dim), int(n_rows),
+                               int(n_policies), buf, len(PLAN_KEYS))
+    if n < 0:
+        abi.check(n)
+    return dict(zip(PLAN_KEYS, buf))
+
+
 def pack_mlp3(w1: torch.Tensor, w2: Optional[torch.Tensor], w3: torch.Tensor, layout: Optional[int] = None):
     """Torch Linear weights ([H1, L], [H2, H1], [KO, H2]) -> (w1p, w2p, w3p) fragment order;
     w2 None: the one-hidden-layer form ([H1, L], [KO, H1] -> (w1p, None, w3p)).
@@ -155,9 +172,9 @@ class _Pack:
 
 
 def _cached_pack(l1: nn.Module, slot, weights, cur, build):
-    """The head actors' pack cached on the first Linear under `slot`, by mlp3_forward's rules: rebuilt
-    by build() when any of `weights` changed (version counters) or moved; ordered after its packing
-    kernels on another stream."""
+    """A pack cached on the first Linear under `slot`: rebuilt by build() when any of `weights` changed
+    (version counters) or moved. cur: the stream the pack is used on (a pack built on another stream is
+    ordered after its packing kernels); None: on the host, nothing to order."""
     packs = getattr(l1, "_msc_packs", None)
     if packs is None:
         packs = l1._msc_packs = {}
@@ -167,9 +184,10 @@ def _cached_pack(l1: nn.Module, slot, weights, cur, build):
         pk.tensors = build()
         pk.key = key
         pk.stream = cur
-        pk.event = torch.cuda.Event()
-        pk.event.record(cur)
-    elif pk.stream != cur:
+        if cur is not None:
+            pk.event = torch.cuda.Event()
+            pk.event.record(cur)
+    elif pk.stream != cur and cur is not None:
         # packed on another stream (e.g. the main stream of a multi-lane rollout): order this
         # stream after the packing kernels, and keep the pack's memory alive for this stream's use
         cur.wait_event(pk.event)
@@ -182,6 +200,32 @@ def _cached_pack(l1: nn.Module, slot, weights, cur, build):
 def sample_fusable(mods) -> bool:
     """True when the fused kernel for mods can also sample the actions (VALU output layer)."""
     return fused_layers(mods) > 0 and w3_layout(mods[-1].out_features) == 1
+
+
+def _pre1_rows(pre1: torch.Tensor, n: int, group: int, H1: int) -> torch.Tensor:
+    """pre1 as the kernels read it: f32 [n / group, H1]."""
+    pre1 = pre1.float().contiguous()
+    if group < 1 or n % group or pre1.shape != (n // group, H1):
+        raise ValueError(f"pre1 must be [{n // max(group, 1)}, {H1}] for {n} rows in groups of {group}")
+    return pre1
+
+
+def _vp(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _gaussian_epilogue(sample, n: int, KO: int, n_policies: Optional[int] = None):
+    """MscGaussianEpilogue of sample = (log_std [rows, KO], logstd_floor, eps, actions, logp, clipped) for n
+    rows of KO outputs; n_policies: log_std has one row, or one per policy."""
+    ls, floor, eps, act, logp, clipped = sample
+    for t in (ls, eps, act, logp, clipped):
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            raise ValueError("sampling buffers must be contiguous float32 CUDA tensors")
+    if eps.numel() != n * KO or act.numel() != n * KO or clipped.numel() != n * KO or logp.numel() != n \
+            or ls.dim() != 2 or ls.shape[1] != KO or (n_policies is not None and ls.shape[0] not in (1, n_policies)):
+        raise ValueError("sampling buffers do not match the MLP's rows / outputs" if n_policies is None else
+                         "sampling buffers do not match the MLPs' rows / outputs / policies")
+    return abi.MscGaussianEpilogue(_vp(ls), int(ls.shape[0]), C.c_float(floor), _vp(eps), _vp(act), _vp(logp), _vp(clipped))
 
 
 def mlp3_forward(mods, x: torch.Tensor, out: Optional[torch.Tensor] = None, *, w1: Optional[torch.Tensor] = None,
@@ -204,66 +248,36 @@ def mlp3_forward(mods, x: torch.Tensor, out: Optional[torch.Tensor] = None, *, w
         raise ValueError(f"input has {x.shape[-1]} features, the MLP expects {L}")
     # pack cache on the first Linear (one per first-layer weight view): rebuilt when any weight
     # changes (version counters) or moves
-    packs = getattr(l1, "_msc_packs", None)
-    if packs is None:
-        packs = l1._msc_packs = {}
-    pk = packs.setdefault((w1.shape, w1.stride(), w1.storage_offset()), _Pack())
     weights = (w1, l3.weight) if l2 is None else (w1, l2.weight, l3.weight)
-    key = tuple((p.data_ptr(), p._version) for p in weights)
     cur = torch.cuda.current_stream(x.device)
-    if pk.key != key:
-        pk.tensors = pack_mlp3(w1, None if l2 is None else l2.weight, l3.weight)
-        pk.key = key
-        pk.stream = cur
-        pk.event = torch.cuda.Event()
-        pk.event.record(cur)
-    elif pk.stream != cur:
-        # packed on another stream (e.g. the main stream of a multi-lane rollout): order this
-        # stream after the packing kernels, and keep the pack's memory alive for this stream's use
-        cur.wait_event(pk.event)
-        for t in pk.tensors:
-            if t is not None:
-                t.record_stream(cur)
-    w1p, w2p, w3p = pk.tensors
-    lead = x.shape[:-1]
-    xf = x.reshape(-1, L)
-    if xf.dtype != torch.float32 or not xf.is_contiguous():
-        xf = xf.float().contiguous()
+    w1p, w2p, w3p = _cached_pack(l1, (w1.shape, w1.stride(), w1.storage_offset()), weights, cur,
+                                 lambda: pack_mlp3(w1, None if l2 is None else l2.weight, l3.weight))
+    lead, xf = x.shape[:-1], _rows(x, L)
     n = xf.shape[0]
     if pre1 is not None:
-        pre1 = pre1.float().contiguous()
-        if group < 1 or n % group or pre1.shape != (n // group, l1.out_features):
-            raise ValueError(f"pre1 must be [{n // max(group, 1)}, {l1.out_features}] for {n} rows in groups of {group}")
-    vp = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        pre1 = _pre1_rows(pre1, n, group, l1.out_features)
     st = C.c_void_p(cur.cuda_stream)
     b1, b3 = (m.bias.detach().float().contiguous() for m in (l1, l3))
     if sample is not None:
-        ls, floor, eps, act, logp, clipped = sample
-        for t in (ls, eps, act, logp, clipped):
-            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-                raise ValueError("sampling buffers must be contiguous float32 CUDA tensors")
-        if eps.numel() != n * KO or act.numel() != n * KO or clipped.numel() != n * KO or logp.numel() != n \
-                or ls.dim() != 2 or ls.shape[1] != KO:
-            raise ValueError("sampling buffers do not match the MLP's rows / outputs")
-        ep = abi.MscGaussianEpilogue(vp(ls), int(ls.shape[0]), C.c_float(floor), vp(eps), vp(act), vp(logp), vp(clipped))
+        ep = _gaussian_epilogue(sample, n, KO)
         if l2 is None:
-            abi.check(abi.lib().msc_mlp2_relu_forward_sampled(vp(xf), n, L, l1.out_features, KO, vp(w1p), vp(b1), vp(w3p),
-                                                              vp(b3), vp(out), vp(pre1), int(group), C.byref(ep), st))
+            abi.check(abi.lib().msc_mlp2_relu_forward_sampled(_vp(xf), n, L, l1.out_features, KO, _vp(w1p), _vp(b1), _vp(w3p),
+                                                              _vp(b3), _vp(out), _vp(pre1), int(group), C.byref(ep), st))
         else:
             b2 = l2.bias.detach().float().contiguous()
-            abi.check(abi.lib().msc_mlp3_relu_forward_sampled(vp(xf), n, L, l1.out_features, l2.out_features, KO,
-                                                              vp(w1p), vp(b1), vp(w2p), vp(b2), vp(w3p), vp(b3), vp(out),
-                                                              vp(pre1), int(group), C.byref(ep), st))
+            abi.check(abi.lib().msc_mlp3_relu_forward_sampled(_vp(xf), n, L, l1.out_features, l2.out_features, KO,
+                                                              _vp(w1p), _vp(b1), _vp(w2p), _vp(b2), _vp(w3p), _vp(b3), _vp(out),
+                                                              _vp(pre1), int(group), C.byref(ep), st))
         return None if out is None else out.reshape(*lead, KO)
     if out is None:
         out = torch.empty((n, KO), device=x.device, dtype=torch.float32)
     if l2 is None:
-        abi.check(abi.lib().msc_mlp2_relu_forward(vp(xf), n, L, l1.out_features, KO, vp(w1p), vp(b1), vp(w3p), vp(b3),
-                                                  vp(out), vp(pre1), int(group), st))
+        abi.check(abi.lib().msc_mlp2_relu_forward(_vp(xf), n, L, l1.out_features, KO, _vp(w1p), _vp(b1), _vp(w3p), _vp(b3),
+                                                  _vp(out), _vp(pre1), int(group), st))
     else:
         b2 = l2.bias.detach().float().contiguous()
-        abi.check(abi.lib().msc_mlp3_relu_forward(vp(xf), n, L, l1.out_features, l2.out_features, KO, vp(w1p), vp(b1),
-                                                  vp(w2p), vp(b2), vp(w3p), vp(b3), vp(out), vp(pre1), int(group), st))
+        abi.check(abi.lib().msc_mlp3_relu_forward(_vp(xf), n, L, l1.out_features, l2.out_features, KO, _vp(w1p), _vp(b1),
+                                                  _vp(w2p), _vp(b2), _vp(w3p), _vp(b3), _vp(out), _vp(pre1), int(group), st))
     return out.reshape(*lead, KO)
 
 
@@ -393,15 +407,12 @@ def musigma_forward(mods, head, x: torch.Tensor, dist_out: Optional[torch.Tensor
     lead, xf = x.shape[:-1], _rows(x, L)
     n = xf.shape[0]
     if pre1 is not None:
-        pre1 = pre1.float().contiguous()
-        if group < 1 or n % group or pre1.shape != (n // group, l1.out_features):
-            raise ValueError(f"pre1 must be [{n // max(group, 1)}, {l1.out_features}] for {n} rows in groups of {group}")
+        pre1 = _pre1_rows(pre1, n, group, l1.out_features)
     if sample is None and dist_out is None:
         dist_out = torch.empty((n, 2 * K), device=x.device, dtype=torch.float32)
     if dist_out is not None and not (dist_out.is_cuda and dist_out.dtype == torch.float32
                                      and dist_out.is_contiguous() and dist_out.numel() == n * 2 * K):
         raise ValueError("dist_out must be a contiguous float32 CUDA tensor of rows x 2K")
-    vp = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
     eps = act = logp = clipped = None
     if sample is not None:
         eps, act, logp, clipped = sample
@@ -412,17 +423,17 @@ def musigma_forward(mods, head, x: torch.Tensor, dist_out: Optional[torch.Tensor
             raise ValueError("sampling buffers do not match the MLP's rows / actions")
     from .rollout import LOG_STD_MAX, LOG_STD_MIN
     ep = abi.MscMuSigmaEpilogue(_ACT_CODE[type(head.mu_activation)], _ACT_CODE[type(head.sigma_activation)],
-                                C.c_float(LOG_STD_MIN), C.c_float(LOG_STD_MAX), vp(eps), vp(act), vp(logp),
-                                vp(clipped), vp(dist_out))
+                                C.c_float(LOG_STD_MIN), C.c_float(LOG_STD_MAX), _vp(eps), _vp(act), _vp(logp),
+                                _vp(clipped), _vp(dist_out))
     st = C.c_void_p(cur.cuda_stream)
     b1 = l1.bias.detach().float().contiguous()
     if l2 is None:
-        abi.check(abi.lib().msc_mlp2_relu_musigma(vp(xf), n, L, l1.out_features, K, vp(w1p), vp(b1), vp(whp), vp(b_eff),
-                                                  vp(pre1), int(group), C.byref(ep), st))
+        abi.check(abi.lib().msc_mlp2_relu_musigma(_vp(xf), n, L, l1.out_features, K, _vp(w1p), _vp(b1), _vp(whp), _vp(b_eff),
+                                                  _vp(pre1), int(group), C.byref(ep), st))
     else:
         b2 = l2.bias.detach().float().contiguous()
-        abi.check(abi.lib().msc_mlp3_relu_musigma(vp(xf), n, L, l1.out_features, l2.out_features, K, vp(w1p), vp(b1),
-                                                  vp(w2p), vp(b2), vp(whp), vp(b_eff), vp(pre1), int(group),
+        abi.check(abi.lib().msc_mlp3_relu_musigma(_vp(xf), n, L, l1.out_features, l2.out_features, K, _vp(w1p), _vp(b1),
+                                                  _vp(w2p), _vp(b2), _vp(whp), _vp(b_eff), _vp(pre1), int(group),
                                                   C.byref(ep), st))
     return None if dist_out is None else dist_out.reshape(*lead, 2 * K)
 
@@ -442,16 +453,15 @@ def musigma_folded(mods, head, x: torch.Tensor):
     lead, xf = x.shape[:-1], _rows(x, L)
     n = xf.shape[0]
     out = torch.empty((n, 2 * K), device=x.device, dtype=torch.float32)
-    vp = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
     st = C.c_void_p(cur.cuda_stream)
     b1 = l1.bias.detach().float().contiguous()
     if l2 is None:
-        abi.check(abi.lib().msc_mlp2_relu_forward(vp(xf), n, L, l1.out_features, 2 * K, vp(w1p), vp(b1), vp(w3p),
-                                                  vp(b_eff), vp(out), None, 1, st))
+        abi.check(abi.lib().msc_mlp2_relu_forward(_vp(xf), n, L, l1.out_features, 2 * K, _vp(w1p), _vp(b1), _vp(w3p),
+                                                  _vp(b_eff), _vp(out), None, 1, st))
     else:
         b2 = l2.bias.detach().float().contiguous()
-        abi.check(abi.lib().msc_mlp3_relu_forward(vp(xf), n, L, l1.out_features, l2.out_features, 2 * K, vp(w1p), vp(b1),
-                                                  vp(w2p), vp(b2), vp(w3p), vp(b_eff), vp(out), None, 1, st))
+        abi.check(abi.lib().msc_mlp3_relu_forward(_vp(xf), n, L, l1.out_features, l2.out_features, 2 * K, _vp(w1p), _vp(b1),
+                                                  _vp(w2p), _vp(b2), _vp(w3p), _vp(b_eff), _vp(out), None, 1, st))
     from .rollout import LOG_STD_MAX, LOG_STD_MIN
     mu, ls = out[:, :K], out[:, K:]
     if head.mu_activation is not None:
@@ -540,21 +550,10 @@ def wide_forward(mods, x: torch.Tensor, out: Optional[torch.Tensor] = None, *, s
     lead, xf = x.shape[:-1], _rows(x, L)
     n = xf.shape[0]
     if pre1 is not None:
-        pre1 = pre1.float().contiguous()
-        if group < 1 or n % group or pre1.shape != (n // group, l1.out_features):
-            raise ValueError(f"pre1 must be [{n // max(group, 1)}, {l1.out_features}] for {n} rows in groups of {group}")
-    vp = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
+        pre1 = _pre1_rows(pre1, n, group, l1.out_features)
     ep = None
     if sample is not None:
-        ls, floor, eps, act, logp, clipped = sample
-        for t in (ls, eps, act, logp, clipped):
-            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-                raise ValueError("sampling buffers must be contiguous float32 CUDA tensors")
-        if eps.numel() != n * KO or act.numel() != n * KO or clipped.numel() != n * KO or logp.numel() != n \
-                or ls.dim() != 2 or ls.shape[1] != KO:
-            raise ValueError("sampling buffers do not match the MLP's rows / outputs")
-        ep = C.byref(abi.MscGaussianEpilogue(vp(ls), int(ls.shape[0]), C.c_float(floor), vp(eps), vp(act), vp(logp),
-                                             vp(clipped)))
+        ep = C.byref(_gaussian_epilogue(sample, n, KO))
     elif out is None:
         out = torch.empty((n, KO), device=x.device, dtype=torch.float32)
     if out is not None and not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
@@ -563,12 +562,12 @@ def wide_forward(mods, x: torch.Tensor, out: Optional[torch.Tensor] = None, *, s
     st = C.c_void_p(cur.cuda_stream)
     b1, b3 = (m.bias.detach().float().contiguous() for m in (l1, l3))
     if l2 is None:
-        abi.check(abi.lib().msc_mlp2_relu_wide(vp(xf), n, L, l1.out_features, KO, vp(w1p), vp(b1), vp(w3p), vp(b3),
-                                               vp(out), vp(pre1), int(group), ep, st))
+        abi.check(abi.lib().msc_mlp2_relu_wide(_vp(xf), n, L, l1.out_features, KO, _vp(w1p), _vp(b1), _vp(w3p), _vp(b3),
+                                               _vp(out), _vp(pre1), int(group), ep, st))
     else:
         b2 = l2.bias.detach().float().contiguous()
-        abi.check(abi.lib().msc_mlp3_relu_wide(vp(xf), n, L, l1.out_features, l2.out_features, KO, vp(w1p), vp(b1),
-                                               vp(w2p), vp(b2), vp(w3p), vp(b3), vp(out), vp(pre1), int(group), ep, st))
+        abi.check(abi.lib().msc_mlp3_relu_wide(_vp(xf), n, L, l1.out_features, l2.out_features, KO, _vp(w1p), _vp(b1),
+                                               _vp(w2p), _vp(b2), _vp(w3p), _vp(b3), _vp(out), _vp(pre1), int(group), ep, st))
     return None if out is None else out.reshape(*lead, KO)
 
 
@@ -643,16 +642,7 @@ def multi_pack(mods_list, w1s=None, cur=None):
         return (w1p, w2p, w3p, bs[0], bs[1] if nl == 3 else None, bs[-1])
 
     slot = ("multi", len(mods_list), w1s[0].shape, w1s[0].stride(), w1s[0].storage_offset())
-    if cur is not None:
-        return _cached_pack(l1, slot, weights, cur, build)
-    packs = getattr(l1, "_msc_packs", None)
-    if packs is None:
-        packs = l1._msc_packs = {}
-    pk = packs.setdefault(slot, _Pack())
-    key = tuple((p.data_ptr(), p._version) for p in weights)
-    if pk.key != key:
-        pk.tensors, pk.key = build(), key
-    return pk.tensors
+    return _cached_pack(l1, slot, weights, cur, build)
 
 
 def multi_forward(mods_list, x: torch.Tensor, out: Optional[torch.Tensor] = None, *, w1=None,
@@ -683,18 +673,9 @@ def multi_forward(mods_list, x: torch.Tensor, out: Optional[torch.Tensor] = None
         pre1 = pre1.float().contiguous()
         if pre1.shape != (n, H1):
             raise ValueError(f"pre1 must be [{n}, {H1}]")
-    vp = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
     ep = None
     if sample is not None:
-        ls, floor, eps, act, logp, clipped = sample
-        for t in (ls, eps, act, logp, clipped):
-            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
-                raise ValueError("sampling buffers must be contiguous float32 CUDA tensors")
-        if eps.numel() != n * KO or act.numel() != n * KO or clipped.numel() != n * KO or logp.numel() != n \
-                or ls.dim() != 2 or ls.shape[1] != KO or ls.shape[0] not in (1, NP):
-            raise ValueError("sampling buffers do not match the MLPs' rows / outputs / policies")
-        ep = C.byref(abi.MscGaussianEpilogue(vp(ls), int(ls.shape[0]), C.c_float(floor), vp(eps), vp(act), vp(logp),
-                                             vp(clipped)))
+        ep = C.byref(_gaussian_epilogue(sample, n, KO, NP))
     elif out is None:
         out = torch.empty((n, KO), device=x.device, dtype=torch.float32)
     if out is not None and not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
@@ -702,9 +683,9 @@ def multi_forward(mods_list, x: torch.Tensor, out: Optional[torch.Tensor] = None
         raise ValueError("out must be a contiguous float32 CUDA tensor of rows x outputs")
     st = C.c_void_p(cur.cuda_stream)
     if nl == 2:
-        abi.check(abi.lib().msc_mlp2_relu_multi(vp(xf), n, NP, L, H1, KO, vp(w1p), vp(b1), vp(w3p), vp(b3), vp(out),
-                                                vp(pre1), ep, st))
+        abi.check(abi.lib().msc_mlp2_relu_multi(_vp(xf), n, NP, L, H1, KO, _vp(w1p), _vp(b1), _vp(w3p), _vp(b3), _vp(out),
+                                                _vp(pre1), ep, st))
     else:
-        abi.check(abi.lib().msc_mlp3_relu_multi(vp(xf), n, NP, L, H1, H2, KO, vp(w1p), vp(b1), vp(w2p), vp(b2), vp(w3p),
-                                                vp(b3), vp(out), vp(pre1), ep, st))
+        abi.check(abi.lib().msc_mlp3_relu_multi(_vp(xf), n, NP, L, H1, H2, KO, _vp(w1p), _vp(b1), _vp(w2p), _vp(b2), _vp(w3p),
+                                                _vp(b3), _vp(out), _vp(pre1), ep, st))
     return None if out is None else out.reshape(*lead, KO)
