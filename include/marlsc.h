@@ -662,6 +662,48 @@ int msc_mlp2_relu_musigma(const float* x, int64_t n_rows, int32_t in_dim, int32_
 int msc_mlp_plan(int32_t family, int32_t hidden1, int32_t hidden2, int32_t out_dim, int64_t n_rows, int32_t n_policies,
                  int32_t* out, int32_t n);
 
+/* The parameter gradients of a plain ReLU MLP in place of torch autograd through the module
+ * MLPArchitecture.build returns (architectures/mlp.py:14-60) inside PPOTorchLearner.compute_gradients:
+ * for y = W3 relu(W2 relu(W1 x + b1) + b2) + b3 (hidden2 = 0: y = W3 relu(W1 x + b1) + b3) and an upstream
+ * gradient d_out [n_rows][out_dim] (msc_ppo_loss's grad_mean / grad_values, or autograd's),
+ *   g_w3 = scale d_out^T h_last, g_b3 = scale sum_rows d_out, d_last = (z_last > 0) . W3^T d_out, and so on down
+ * to g_w1 = scale d1^T x. No input gradient is computed (the observations are leaves).
+ * The supported set is msc_mlp{3,2}_relu_forward's: hidden1, hidden2 in {64, 128, 256, 512}, or hidden2 = 0 and
+ * hidden1 a multiple of 32 up to 1024; in_dim <= 1024, out_dim <= 32.
+ * Inputs (f32 device buffers, stream-ordered): x [n_rows][in_dim]; w1p, b1, w2p, b2 exactly as the forward
+ * entry points take them (w3 is staged in LDS by each block when out_dim x hidden_last floats fit 64 KiB, which
+ * they always do with two hidden layers); w2tp the pack of W2^T (the w2p index map applied to the transposed matrix:
+ * w2tp[t1][s4][lane][i] = W2[32 t2 + rho(r, h)][32 t1 + c], 4 s4 + i = 16 t2 + r; marlsc/mlp.py:pack_w2t; NULL with
+ * one hidden layer, as are w2p, b2, g_w2, g_b2); w3 [out_dim][hidden_last] in torch's own layout (not the
+ * forward's w3p: the layout does not depend on out_dim here). b1, b2, the packs, w3 and the workspace must be
+ * 16-byte aligned.
+ * Outputs in torch's layouts, ready to be .grad: g_w1 [hidden1][in_dim], g_b1 [hidden1], g_w2 [hidden2][hidden1],
+ * g_b2 [hidden2], g_w3 [out_dim][hidden_last], g_b3 [out_dim]. scale multiplies every gradient; accumulate = 1
+ * adds to what the buffers hold, 0 overwrites (prior contents, NaN included, are ignored). n_rows = 0 writes
+ * zeros (accumulate = 0) or nothing (accumulate = 1) and launches nothing that reads x.
+ * Nothing is saved by the forward: the hidden pre-activations are recomputed from x with the forward kernels'
+ * packs in the forward kernels' accumulation order, so the ReLU masks are those of msc_mlp{3,2}_relu_forward
+ * bit for bit. The mask is z > 0: zero gradient at z == 0, as torch.
+ * Deterministic: no atomics; the reduction over rows runs in tiles of 32, split-K slices and rounds that are
+ * functions of the shape arguments alone, added in a fixed order, so two calls on the same inputs give the
+ * same bits. Exactness: products are exact in f32 and every sum is accumulated in f32, except the bias gradients'
+ * sums over rows, which are accumulated in f64 and rounded to f32 once per slice; with integer x, weights,
+ * biases and d_out whose absolute-value evaluation stays below 2^24 at every partial sum (and a power-of-two
+ * scale), all six gradients equal the int64 evaluation bit for bit, whatever the reduction order. With real
+ * data the order differs from torch's GEMMs: compare at f32 GEMM tolerance. No non-finite-row guarantee: a NaN
+ * row reaches the sums.
+ * workspace: msc_mlp_relu_backward_workspace(...) bytes of device memory (-1 for an unsupported shape), owned by
+ * the caller and free again once the stream has passed the call. The bytes are monotone in n_rows and capped:
+ * rows are processed in rounds of at most 16,384 (hidden1 + hidden2 <= 512) or 8,192 rows inside the call,
+ * each accumulated onto the outputs, so the workspace never exceeds 64 MiB of operands (2 (hidden1 + hidden2)
+ * floats per row of a round) plus 8 slices of partials (one padded copy of the six gradients each).
+ * An unsupported shape or a NULL required pointer returns an error and writes nothing. */
+int64_t msc_mlp_relu_backward_workspace(int64_t n_rows, int32_t in_dim, int32_t hidden1, int32_t hidden2, int32_t out_dim);
+int msc_mlp_relu_backward(const float* x, int64_t n_rows, int32_t in_dim, int32_t hidden1, int32_t hidden2, int32_t out_dim,
+                          const float* w1p, const float* b1, const float* w2p, const float* b2, const float* w2tp,
+                          const float* w3, const float* d_out, float scale, int32_t accumulate, float* g_w1, float* g_b1,
+                          float* g_w2, float* g_b2, float* g_w3, float* g_b3, void* workspace, msc_stream_t stream);
+
 /* One time step of a GRU network for n_rows rows in one launch: replaces the module
  * GRUArchitecture.build returns (architectures/gru.py:14-85: nn.GRU(batch_first) -> output_proj =
  * [act,] Linear [, act]) as BaseRLModule._forward_gru steps it on a [B, obs_dim] input

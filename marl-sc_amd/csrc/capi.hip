@@ -18,6 +18,7 @@
 #include "../../include/marlsc.h"
 #include "env.hpp"
 #include "env_plan.hpp"
+#include "mlp_backward.hpp"
 #include "mlp_dispatch.hpp"
 #include "rng.hpp"
 
@@ -1262,6 +1263,48 @@ int msc_mlp_plan(int32_t family, int32_t hidden1, int32_t hidden2, int32_t out_d
   const int m = n < MSC_MLP_PLAN_N ? n : MSC_MLP_PLAN_N;
   for (int i = 0; i < m; i++) out[i] = v[i];
   return m;
+}
+
+// the parameter gradients of the plain fused MLPs (mlp_backward.hip; replaces torch autograd through
+// MLPArchitecture.build's module inside PPOTorchLearner.compute_gradients). The shape rules are the forward entry
+// points', through their argument check: w3 stands where they take w3p and d_out where they take b3.
+static const MlpEntry MLP_BWD{"fused", nullptr, true, 32, false};
+
+int64_t msc_mlp_relu_backward_workspace(int64_t n_rows, int32_t in_dim, int32_t hidden1, int32_t hidden2, int32_t out_dim) {
+  const bool hidden = hidden2 != 0 ? mlp_hidden_ok(hidden1) && mlp_hidden_ok(hidden2) : mlp2_supported(hidden1);
+  if (n_rows < 0 || in_dim < 1 || in_dim > 1024 || out_dim < 1 || out_dim > 32 || !hidden) return -1;
+  return mlp_backward_workspace_bytes(n_rows, in_dim, hidden1, hidden2, out_dim);
+}
+
+int msc_mlp_relu_backward(const float* x, int64_t n_rows, int32_t in_dim, int32_t hidden1, int32_t hidden2, int32_t out_dim,
+                          const float* w1p, const float* b1, const float* w2p, const float* b2, const float* w2tp,
+                          const float* w3, const float* d_out, float scale, int32_t accumulate, float* g_w1, float* g_b1,
+                          float* g_w2, float* g_b2, float* g_w3, float* g_b3, void* workspace, msc_stream_t stream) {
+  const bool two = hidden2 != 0;
+  if (const int r = mlp_check(MLP_BWD, two, {x, n_rows, in_dim, hidden1, hidden2, out_dim, w1p, b1, w2p, b2, w3, d_out,
+                                             nullptr, nullptr, 1}, g_w1))
+    return r;
+  if (!g_b1 || !g_w3 || !g_b3 || (two && (!w2tp || !g_w2 || !g_b2)) || (n_rows > 0 && !workspace))
+    return set_err(-1, "null argument");
+  if (((uintptr_t)w2tp | (uintptr_t)workspace) & 15) return set_err(-1, "w2tp and the workspace must be 16-byte aligned");
+  const hipStream_t st = (hipStream_t)stream;
+  const int HL = two ? hidden2 : hidden1;
+  if (n_rows == 0) {  // the sum over no rows: zeros, or nothing to add; x is not read
+    if (accumulate) return 0;
+    HIP_TRY(hipMemsetAsync(g_w1, 0, sizeof(float) * hidden1 * in_dim, st));
+    HIP_TRY(hipMemsetAsync(g_b1, 0, sizeof(float) * hidden1, st));
+    if (two) {
+      HIP_TRY(hipMemsetAsync(g_w2, 0, sizeof(float) * hidden2 * hidden1, st));
+      HIP_TRY(hipMemsetAsync(g_b2, 0, sizeof(float) * hidden2, st));
+    }
+    HIP_TRY(hipMemsetAsync(g_w3, 0, sizeof(float) * out_dim * HL, st));
+    HIP_TRY(hipMemsetAsync(g_b3, 0, sizeof(float) * out_dim, st));
+    return 0;
+  }
+  const MlpBwdArgs a{x, n_rows, in_dim, hidden1, hidden2, out_dim, w1p, b1, w2p, b2, w2tp, w3, d_out, scale,
+                     accumulate ? 1 : 0, g_w1, g_b1, g_w2, g_b2, g_w3, g_b3};
+  HIP_TRY(launch_mlp_backward(a, workspace, st));
+  return 0;
 }
 
 // GRU networks (replaces GRUArchitecture's gru -> output_proj as BaseRLModule._forward_gru steps it,

@@ -23,6 +23,9 @@ With one policy per agent (parameter_sharing: false) the W same-shaped actors, a
 one launch each over the rows [..., W, L] (msc_mlp{2,3}_relu_multi, csrc/mlp_multi.hip; multi_forward at
 the end of this file; opt-in, MSC_MULTI_MLP=1).
 
+The plain MLPs can also be trained through the kernels (train_forward: the inference kernel forward, one
+msc_mlp_relu_backward call backward, csrc/mlp_backward.hip; opt-in, MSC_FUSED_MLP_GRAD=1): the last section.
+
 There is no CPU fallback: a CUDA tensor on a build without libmarlsc raises (abi.lib()).
 """
 from __future__ import annotations
@@ -131,6 +134,15 @@ def pack_mlp3(w1: torch.Tensor, w2: Optional[torch.Tensor], w3: torch.Tensor, la
     w2p = w2.detach().float().reshape(-1)[i2].contiguous() if w2 is not None else None
     w3p = torch.where(v3, w3.detach().float().reshape(-1)[i3], zero)
     return w1p.contiguous(), w2p, w3p.contiguous()
+
+
+def pack_w2t(w2: torch.Tensor) -> torch.Tensor:
+    """Torch Linear weight [H2, H1] -> the pack of its transpose for msc_mlp_relu_backward's dgrad pass
+    d1 = W2^T d2: pack_mlp3's layer-2 index map (the `i2` of _index_maps) on the [H1, H2] matrix W2^T, i.e.
+    w2tp[t1][s4][lane][i] = W2[32 t2 + rho(r, h)][32 t1 + c], 4 s4 + i = 16 t2 + r."""
+    H2, H1 = w2.shape
+    i2 = _index_maps(1, H2, H1, 1, w2.device, 0)[2]  # (layer 1 and the output layer of the key are not used)
+    return w2.detach().float().t().contiguous().reshape(-1)[i2].contiguous()
 
 
 def fused_layers(mods, max_out: int = MAX_OUT) -> int:
@@ -689,3 +701,128 @@ def multi_forward(mods_list, x: torch.Tensor, out: Optional[torch.Tensor] = None
         abi.check(abi.lib().msc_mlp3_relu_multi(_vp(xf), n, NP, L, H1, H2, KO, _vp(w1p), _vp(b1), _vp(w2p), _vp(b2), _vp(w3p),
                                                 _vp(b3), _vp(out), _vp(pre1), ep, st))
     return None if out is None else out.reshape(*lead, KO)
+
+
+# ----------------------------------------------------------------------------------------------
+# Training through the fused kernels (opt-in: PPOLearner(fused_mlp=True) / MSC_FUSED_MLP_GRAD=1): the forward
+# is mlp3_forward, the inference kernel, so the learner's forward equals the collector's bit for bit; the
+# backward is one msc_mlp_relu_backward call (csrc/mlp_backward.hip) that recomputes the hidden layers and
+# returns the six parameter gradients in torch's layouts. No input gradient. Not covered (they keep the torch
+# layers): mu/sigma-head backbones, GRU networks and MLP heads over a GRU trunk, the wide (33..128 outputs)
+# actor, and a multi-policy backward (per-agent policies make one call each).
+# ----------------------------------------------------------------------------------------------
+def fused_mlp_default() -> bool:
+    """MSC_FUSED_MLP_GRAD=1 turns the fused MLP backward on where PPOLearner is built with fused_mlp=None."""
+    return os.environ.get("MSC_FUSED_MLP_GRAD", "0") == "1"
+
+
+def backward_workspace_bytes(n_rows: int, in_dim: int, hidden1: int, hidden2: int, out_dim: int) -> int:
+    """msc_mlp_relu_backward_workspace: bytes for n_rows rows (monotone in n_rows, capped), -1 when the shape
+    has no backward kernel. hidden2 = 0: one hidden layer."""
+    return int(abi.lib().msc_mlp_relu_backward_workspace(int(n_rows), int(in_dim), int(hidden1), int(hidden2), int(out_dim)))
+
+
+_BWD_WORKSPACES: Dict[Tuple[int, int], torch.Tensor] = {}
+
+
+def _bwd_workspace(device: torch.device, nbytes: int) -> torch.Tensor:
+    """One workspace per (device, stream), grown on demand and kept (ppo_loss.py:_workspace's rule: calls on
+    one stream are ordered, so a call's last kernel has read the workspace before the next call writes it)."""
+    key = (device.index if device.index is not None else torch.cuda.current_device(),
+           torch.cuda.current_stream(device).cuda_stream)
+    w = _BWD_WORKSPACES.get(key)
+    if w is None or w.numel() * 4 < nbytes:
+        w = torch.empty(-(-nbytes // 4), dtype=torch.float32, device=device)
+        _BWD_WORKSPACES[key] = w
+    return w
+
+
+def trainable(mods) -> bool:
+    """True when train_forward covers mods: fused_layers' set with at most 32 outputs, f32 CUDA parameters."""
+    mods = list(mods)
+    if fused_layers(mods) == 0:
+        return False
+    return all(p.is_cuda and p.dtype == torch.float32 for m in mods[0::2] for p in (m.weight, m.bias))
+
+
+def mlp_backward(mods, x: torch.Tensor, d_out: torch.Tensor, *, scale: float = 1.0, grads=None):
+    """One msc_mlp_relu_backward call: the gradients of mods' parameters for the upstream gradient d_out
+    [..., KO] at the inputs x [..., L] (f32 CUDA), in parameter order (w1, b1[, w2, b2], w3, b3), each in its
+    parameter's shape. grads given (that tuple of contiguous f32 tensors): the call adds to them."""
+    mods = list(mods)
+    nl = fused_layers(mods)
+    if nl == 0:
+        raise ValueError("no fused kernel for this layer sequence (see fused_layers)")
+    l1, l3 = mods[0], mods[-1]
+    l2 = mods[2] if nl == 3 else None
+    L, H1, KO = l1.in_features, l1.out_features, l3.out_features
+    H2 = l2.out_features if l2 is not None else 0
+    if x.shape[-1] != L or d_out.shape[-1] != KO:
+        raise ValueError(f"x / d_out have {x.shape[-1]} / {d_out.shape[-1]} columns, the MLP has {L} inputs and {KO} outputs")
+    xf, df = _rows(x, L), _rows(d_out, KO)
+    n = xf.shape[0]
+    if df.shape[0] != n:
+        raise ValueError(f"d_out has {df.shape[0]} rows for {n} rows of x")
+    cur = torch.cuda.current_stream(xf.device)
+    w1 = l1.weight
+    weights = (w1, l3.weight) if l2 is None else (w1, l2.weight, l3.weight)
+    w1p, w2p, _ = _cached_pack(l1, (w1.shape, w1.stride(), w1.storage_offset()), weights, cur,
+                               lambda: pack_mlp3(w1, None if l2 is None else l2.weight, l3.weight))
+    w2tp = None
+    if l2 is not None:
+        (w2tp,) = _cached_pack(l1, "w2t", (l2.weight,), cur, lambda: (pack_w2t(l2.weight),))
+    lins = (l1, l3) if l2 is None else (l1, l2, l3)
+    params = [p for m in lins for p in (m.weight, m.bias)]
+    accumulate = grads is not None
+    if grads is None:
+        grads = tuple(torch.empty(p.shape, dtype=torch.float32, device=xf.device) for p in params)
+    elif len(grads) != len(params) or any(not (g.is_cuda and g.dtype == torch.float32 and g.is_contiguous()
+                                               and g.shape == p.shape) for g, p in zip(grads, params)):
+        raise ValueError("grads must be contiguous float32 CUDA tensors in the parameters' shapes")
+    ws = _bwd_workspace(xf.device, backward_workspace_bytes(n, L, H1, H2, KO)) if n > 0 else None
+    b1 = l1.bias.detach().float().contiguous()
+    b2 = l2.bias.detach().float().contiguous() if l2 is not None else None
+    w3 = l3.weight.detach().float().contiguous()
+    g = list(grads)
+    gw2, gb2 = (g[2], g[3]) if l2 is not None else (None, None)
+    abi.check(abi.lib().msc_mlp_relu_backward(_vp(xf), n, L, H1, H2, KO, _vp(w1p), _vp(b1), _vp(w2p), _vp(b2), _vp(w2tp),
+                                              _vp(w3), _vp(df), C.c_float(scale), 1 if accumulate else 0, _vp(g[0]), _vp(g[1]),
+                                              _vp(gw2), _vp(gb2), _vp(g[-2]), _vp(g[-1]), _vp(ws), C.c_void_p(cur.cuda_stream)))
+    return tuple(grads)
+
+
+class _TrainForward(torch.autograd.Function):
+    """mods' forward through the inference kernel; the parameters enter as inputs so that autograd hands their
+    gradients on (and checks that none was modified between forward and backward)."""
+
+    @staticmethod
+    def forward(ctx, x, mods, *params):
+        ctx.mods = mods
+        ctx.save_for_backward(x, *params)
+        return mlp3_forward(mods, x)
+
+    @staticmethod
+    def backward(ctx, g):
+        x = ctx.saved_tensors[0]
+        return (None, None) + mlp_backward(ctx.mods, x, g)
+
+
+def train_forward(mods, x: torch.Tensor) -> torch.Tensor:
+    """mods (Linear-ReLU(-Linear-ReLU)-Linear as accepted by fused_layers, at most 32 outputs) applied to x
+    [..., L] under autograd: msc_mlp{3,2}_relu_forward now, one msc_mlp_relu_backward call in backward().
+    x is a leaf of the graph: no gradient flows into it. Raises RuntimeError for non-CUDA or non-float32
+    input (there is no CPU path), ValueError for a layer sequence without a kernel."""
+    mods = list(mods)
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise RuntimeError("train_forward: x must be a CUDA tensor (the fused MLP backward is a HIP kernel; run the "
+                           f"torch layers on {getattr(x, 'device', type(x).__name__)})")
+    if x.dtype != torch.float32:
+        raise RuntimeError(f"train_forward: x must be torch.float32, not {x.dtype}")
+    if x.requires_grad:
+        raise RuntimeError("train_forward: x requires a gradient, and the fused backward computes none for its input")
+    if fused_layers(mods) == 0:
+        raise ValueError("no fused kernel for this layer sequence (see fused_layers)")
+    if not trainable(mods):
+        raise RuntimeError("train_forward: the parameters must be float32 CUDA tensors")
+    params = [p for m in mods[0::2] for p in (m.weight, m.bias)]
+    return _TrainForward.apply(x, tuple(mods), *params)

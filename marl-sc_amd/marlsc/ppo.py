@@ -403,14 +403,23 @@ class PPOLearner:
         return float(np.mean(self.kl_coeffs))
 
     def __init__(self, module: MultiAgentActorCritic, cfg: PPOConfig, *, seed: int = 0,
-                 fused_loss: Optional[bool] = None):
+                 fused_loss: Optional[bool] = None, fused_mlp: Optional[bool] = None):
         """fused_loss: the loss, its statistics and its gradients from the msc_ppo_loss kernel
         (marlsc/ppo_loss.py) instead of ppo_loss under autograd; None reads MSC_FUSED_LOSS (default off).
-        It needs the module on a CUDA device and raises RuntimeError otherwise."""
+        fused_mlp: the plain MLP actors and critics (mlp.trainable: the fused inference kernels' ReLU family,
+        at most 32 outputs, f32) train through mlp.train_forward -- the inference kernel forward, one
+        msc_mlp_relu_backward call backward -- instead of the torch layers; None reads MSC_FUSED_MLP_GRAD
+        (default off). Everything else keeps the torch layers: mu/sigma-head backbones, GRU networks and
+        MLP heads over a GRU trunk, wider actors. Per-agent policies make one call per policy.
+        Either switch needs the module on a CUDA device and raises RuntimeError otherwise."""
         self.module, self.cfg = module, cfg
         self.fused_loss = fused_loss_default() if fused_loss is None else bool(fused_loss)
         if self.fused_loss and next(module.parameters()).device.type != "cuda":
             raise RuntimeError("PPOLearner(fused_loss=True): the fused PPO loss is a HIP kernel and needs the module "
+                               f"on a CUDA device, not {next(module.parameters()).device}")
+        self.fused_mlp = mlp3.fused_mlp_default() if fused_mlp is None else bool(fused_mlp)
+        if self.fused_mlp and next(module.parameters()).device.type != "cuda":
+            raise RuntimeError("PPOLearner(fused_mlp=True): the fused MLP backward is a HIP kernel and needs the module "
                                f"on a CUDA device, not {next(module.parameters()).device}")
         self.opt = torch.optim.Adam(module.parameters(), lr=cfg.lr_at(0))
         # RLlib keeps one adaptive KL coefficient per module
@@ -426,6 +435,14 @@ class PPOLearner:
             return [torch.arange(S * W, device=device)]
         return [torch.arange(S, device=device) * W + w for w in range(W)]
 
+    def _mlp(self, net: nn.Module, x: torch.Tensor) -> torch.Tensor:
+        """net(x) for an MLP actor / critic on gathered observation rows (leaves of the graph): through the
+        fused kernels when the switch is on and they cover it, else the torch layers."""
+        if self.fused_mlp and x.is_cuda and x.dtype == torch.float32 and not x.requires_grad \
+                and isinstance(net, nn.Sequential) and mlp3.trainable(net):
+            return mlp3.train_forward(net, x)
+        return net(x)
+
     def _forward(self, policy: "AgentModule", obs: torch.Tensor, rows: torch.Tensor):
         """(mean, log_std, values) of `policy` on batch rows (flat ids s * W + w of obs [S, W, L])."""
         rc = self.module.rc
@@ -437,9 +454,11 @@ class PPOLearner:
         if policy.head_mode:  # state-dependent log_std from the head, no free parameter
             mean, log_std = policy.dist(full if rc.actor_obs_type == "global" else local)
         else:
-            mean = policy.actor(full if rc.actor_obs_type == "global" else local)
+            mean = self._mlp(policy.actor, full if rc.actor_obs_type == "global" else local)
             log_std = torch.clamp(policy.log_std, min=rc.logstd_floor).expand_as(mean)
-        values = policy.critic(full if rc.critic_obs_type == "global" else local).squeeze(-1)
+        # (a mu/sigma-head module keeps the torch layers as a whole, critic included)
+        critic = policy.critic if policy.head_mode else (lambda x: self._mlp(policy.critic, x))
+        values = critic(full if rc.critic_obs_type == "global" else local).squeeze(-1)
         return mean, log_std, values
 
     # -- GRU networks: a training sample is a sequence (chunk c, env e, agent w) of S = max_seq_len
@@ -714,9 +733,11 @@ def compute_obs_statistics(env_config: Any, seed_manager, mode: str = "meanstd_c
 class PPOTrainer:
     def __init__(self, env_config: Any, cfg: PPOConfig, *, root_seed: int = 42, n_envs: Optional[int] = None,
                  rollout_len: Optional[int] = None, device: int = 0, env_meta: Optional[Dict[str, Any]] = None,
-                 eval_seed: Optional[int] = None, multi_mlp: Optional[bool] = None):
+                 eval_seed: Optional[int] = None, multi_mlp: Optional[bool] = None,
+                 fused_loss: Optional[bool] = None, fused_mlp: Optional[bool] = None):
         """multi_mlp: passed to MultiAgentActorCritic (per-agent policies in one launch; None reads
-        MSC_MULTI_MLP)."""
+        MSC_MULTI_MLP). fused_loss / fused_mlp: passed to PPOLearner (None reads MSC_FUSED_LOSS /
+        MSC_FUSED_MLP_GRAD)."""
         from .seeding import SeedManager
         from .spec import EnvSpec
         from .vec_env import VecInventoryEnv
@@ -758,7 +779,8 @@ class PPOTrainer:
         if self.world > 1:  # identical initial weights on every rank
             for p in self.module.parameters():
                 dist.broadcast(p.data, src=0)
-        self.learner = PPOLearner(self.module, cfg, seed=self.train_seed + self.rank)
+        self.learner = PPOLearner(self.module, cfg, seed=self.train_seed + self.rank, fused_loss=fused_loss,
+                                  fused_mlp=fused_mlp)
         # advantages standardised per module (RLlib's GAE connector): one group for the shared policy,
         # one per agent otherwise
         # one noise seed for every rank: the noise is keyed by global env id (msc_normal_keyed)

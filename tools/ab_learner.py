@@ -9,7 +9,10 @@ Shapes: the reference ippo.yaml networks (actor / critic [256], local observatio
 (actor [256, 256], global critic [64, 64], KL term on) with the C3 observation width and K = 5, 8 agents
 sharing one policy; a minibatch of 800 rows out of an 8,000-step batch (64,000 rows), and one of 262,144 rows
 (32,768 envs x 8 agents, the whole batch).
-The two variants are alternated in one process after a warm-up; each sample is one step between two device
+Each step also runs with the fused MLP backward (msc_mlp_relu_backward, PPOLearner(fused_mlp=True), opt-in): step_mlp is
+the torch loss with the MLPs through mlp.train_forward, step_fused_mlp the fused loss with them (the intended fast
+path). A last row runs 8 per-agent policies (ippo.yaml networks) at 800 rows each, one backward call per network.
+The variants are alternated in one process after a warm-up; each sample is one step between two device
 events, the device idle before the first (synchronised). Medians, the 5th .. 95th percentile and the range.
 
   python tools/ab_learner.py [--rounds 100] [--rounds-large 20] [--warmup 10] [--out profiles/ppo_loss/ab_learner.txt]
@@ -34,15 +37,15 @@ def _local_obs_dim() -> int:
     return EnvSpec.from_config(cfg, {"include_warehouse_id": True}).local_obs_dim
 
 
-def _setup(name: str, S: int, W: int, L: int, K: int):
-    """(cfg, module, batch [S, W, ...]) for config_files/algorithms/<name>.yaml with a shared policy."""
+def _setup(name: str, S: int, W: int, L: int, K: int, shared: bool = True):
+    """(cfg, module, batch [S, W, ...]) for config_files/algorithms/<name>.yaml with a shared policy (or W)."""
     from marlsc.ppo import MultiAgentActorCritic, PPOConfig, gaussian_logp
     cfg = PPOConfig.from_algorithm_config(yaml.safe_load(open(REPO / f"config_files/algorithms/{name}.yaml")))
     torch.manual_seed(0)
-    m = MultiAgentActorCritic(W, L, L * W, K, cfg.rollout_config(), True).cuda()
+    m = MultiAgentActorCritic(W, L, L * W, K, cfg.rollout_config(), shared).cuda()
     obs = torch.randn(S, W, L, device="cuda")
     with torch.no_grad():
-        mean = torch.cat([m.policies[0].actor(o) for o in obs.split(4096)])
+        mean = torch.cat([m.policies[0].actor(o) for o in obs.split(4096)])  # (policy 0's mean serves every agent)
         ls = torch.clamp(m.policies[0].log_std, min=m.rc.logstd_floor).expand_as(mean).contiguous()
         act = mean + ls.exp() * torch.randn_like(mean)
         logp = gaussian_logp(act, mean, ls) + 0.1 * torch.randn(S, W, device="cuda")
@@ -72,6 +75,16 @@ class Steps:
         if self.cfg.grad_clip:
             torch.nn.utils.clip_grad_norm_([p for p in self.params if p.grad is not None], self.cfg.grad_clip)
         self.learner.opt.step()
+
+    def with_mlp(self, fn):
+        """fn with the learner's fused_mlp switch on"""
+        def run():
+            self.learner.fused_mlp = True
+            try:
+                return fn()
+            finally:
+                self.learner.fused_mlp = False
+        return run
 
     def torch_step(self):
         from marlsc.ppo import ppo_loss
@@ -104,6 +117,34 @@ class Steps:
         from marlsc.ppo_loss import fused_ppo_loss
         mean, ls, values = leaves
         fused_ppo_loss(self.cfg, mean, ls, values, self.flat, self.idx, 0.2, stats=self.dev_stats)[0].backward()
+
+
+class AgentSteps(Steps):
+    """The same steps over W per-agent policies: every policy's rows idx[w], one optimizer step."""
+
+    def __init__(self, cfg, m, obs, batch, idx):
+        super().__init__(cfg, m, obs, batch, idx)
+        self.params = [p for p in m.parameters()]
+
+    def torch_step(self):
+        from marlsc.ppo import ppo_loss
+        total, host = None, 0.0
+        for pol, idx in zip(self.m.policies, self.idx):
+            b = {k: v[idx] for k, v in self.flat.items()}
+            loss, sts = ppo_loss(self.cfg, *self.learner._forward(pol, self.obs, idx), b, 0.2)
+            host += sum(float(v.detach()) for v in sts.values())
+            total = loss if total is None else total + loss
+        self._finish(total)
+        return host
+
+    def fused_step(self):
+        from marlsc.ppo_loss import fused_ppo_loss
+        total = None
+        for pol, idx in zip(self.m.policies, self.idx):
+            loss, _ = fused_ppo_loss(self.cfg, *self.learner._forward(pol, self.obs, idx), self.flat, idx, 0.2,
+                                     stats=self.dev_stats)
+            total = loss if total is None else total + loss
+        self._finish(total)
 
 
 def _time(variants, rounds, warmup):
@@ -149,7 +190,8 @@ def main() -> int:
             cfg, m, obs, batch = _setup(name, S, W, L, K)
             st = Steps(cfg, m, obs, batch, torch.randperm(S * W, device="cuda")[:rows])
             leaves = st.outputs()
-            t = _time({"step_torch": st.torch_step, "step_fused": st.fused_step}, rounds, args.warmup)
+            t = _time({"step_torch": st.torch_step, "step_fused": st.fused_step, "step_mlp": st.with_mlp(st.torch_step),
+                       "step_fused_mlp": st.with_mlp(st.fused_step)}, rounds, args.warmup)
             t.update(_time({"loss_torch": lambda: st.torch_loss(leaves), "loss_fused": lambda: st.fused_loss(leaves)},
                            rounds, args.warmup))
             res = {"config": name, "rows": rows, "rounds": rounds}
@@ -157,14 +199,34 @@ def main() -> int:
             for k, v in t.items():
                 res[k] = {"median_us": float(np.median(v)), "p05_us": float(np.percentile(v, 5)),
                           "p95_us": float(np.percentile(v, 95)), "min_us": float(v.min()), "max_us": float(v.max())}
-                lines.append(f"  {k:11s} median {res[k]['median_us']:9.1f}   p05 {res[k]['p05_us']:9.1f}   p95 "
+                lines.append(f"  {k:14s} median {res[k]['median_us']:9.1f}   p05 {res[k]['p05_us']:9.1f}   p95 "
                              f"{res[k]['p95_us']:9.1f}   range {res[k]['min_us']:.1f} .. {res[k]['max_us']:.1f}")
             for kind in ("step", "loss"):
                 res[f"{kind}_torch_over_fused"] = res[f"{kind}_torch"]["median_us"] / res[f"{kind}_fused"]["median_us"]
                 lines.append(f"  {kind}: torch / fused = {res[f'{kind}_torch_over_fused']:.3f}")
+            for k, base in (("step_mlp", "step_torch"), ("step_fused_mlp", "step_fused"), ("step_fused_mlp", "step_torch")):
+                res[f"{base}_over_{k}"] = res[base]["median_us"] / res[k]["median_us"]
+                lines.append(f"  {base} / {k} = {res[f'{base}_over_{k}']:.3f}")
             results.append(res)
             del st, leaves, cfg, m, obs, batch
             torch.cuda.empty_cache()
+    # per-agent policies: 8 ippo.yaml policies, 800 rows each out of each agent's 8,000
+    cfg, m, obs, batch = _setup("ippo", 8000, W, L, K, shared=False)
+    idx = [torch.randperm(8000, device="cuda")[:800] * W + w for w in range(W)]
+    st = AgentSteps(cfg, m, obs, batch, idx)
+    t = _time({"step_torch": st.torch_step, "step_fused": st.fused_step, "step_mlp": st.with_mlp(st.torch_step),
+               "step_fused_mlp": st.with_mlp(st.fused_step)}, args.rounds, args.warmup)
+    res = {"config": "ippo per-agent", "rows": 800, "policies": W, "rounds": args.rounds}
+    lines.append(f"ippo.yaml networks, {W} per-agent policies, minibatches of 800 rows each, {args.rounds} rounds")
+    for k, v in t.items():
+        res[k] = {"median_us": float(np.median(v)), "p05_us": float(np.percentile(v, 5)),
+                  "p95_us": float(np.percentile(v, 95)), "min_us": float(v.min()), "max_us": float(v.max())}
+        lines.append(f"  {k:14s} median {res[k]['median_us']:9.1f}   p05 {res[k]['p05_us']:9.1f}   p95 "
+                     f"{res[k]['p95_us']:9.1f}   range {res[k]['min_us']:.1f} .. {res[k]['max_us']:.1f}")
+    for k, base in (("step_mlp", "step_torch"), ("step_fused_mlp", "step_fused"), ("step_fused_mlp", "step_torch")):
+        res[f"{base}_over_{k}"] = res[base]["median_us"] / res[k]["median_us"]
+        lines.append(f"  {base} / {k} = {res[f'{base}_over_{k}']:.3f}")
+    results.append(res)
     text = "\n".join(lines) + "\n"
     print(text)
     print(json.dumps(results))
