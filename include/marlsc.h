@@ -396,6 +396,61 @@ int msc_ppo_loss(const msc_ppo_loss_desc* desc, const float* mean, const float* 
                  int32_t k, float* grad_mean, float* grad_log_std, float* grad_values, float* total, double* stats,
                  void* workspace, msc_stream_t stream);
 
+/* The learner's gradient clip and Adam step in one call: torch.nn.utils.clip_grad_norm_ per group (a group
+ * is one policy: RLlib's learner clips each module's gradients by its own global norm) followed by
+ * torch.optim.Adam.step (no weight decay, no amsgrad) over every tensor of every group, up to rounding order.
+ *   tensors: a HOST array of n_tensors entries {p, g, m, v: float32 device buffers of n elements (the
+ *   parameter, its gradient, exp_avg, exp_avg_sq), group in [0, n_groups)}. The call reads the table while
+ *   it runs and keeps nothing of it: neither the table nor the pointers in it need to stay the same between
+ *   calls. Entries with n = 0 are skipped. The buffers of different entries must not overlap.
+ * Arithmetic. Per group, over the elements of its tensors:
+ *     S = sum (double)g (double)g   in float64, in a fixed order, no atomics;   norm = sqrt(S)
+ *     c = (float)min(1, max_norm / (norm + 1e-6))   in float64, rounded once;   c = 1 when max_norm <= 0
+ * and with b2 = (float)beta2, a1 = (float)(1 - beta1), a2 = (float)(1 - beta2), e = (float)eps,
+ * step_size = (float)(lr / (1 - beta1^step)) and r2 = (float)sqrt(1 - beta2^step), each formed on the host in
+ * float64 and rounded once, per element in float32, one rounding per operation, nothing contracted, sqrt
+ * and / correctly rounded:
+ *     g' = g c
+ *     m' = m + a1 (g' - m)
+ *     v' = b2 v + (a2 g') g'
+ *     p' = p - step_size (m' / (sqrt(v') / r2 + e))
+ * p, m and v are updated in place; write_clipped_grads = 1 also stores g' over g (as the torch clip does),
+ * 0 leaves g untouched. step is the step count after its increment (the first step is 1). Non-finite
+ * gradients propagate as they do in torch; nothing is guaranteed about them.
+ *   norms_out (device f64[n_groups], or NULL): every group's norm, 0 for a group without elements.
+ *   workspace: msc_adam_clip_workspace(n_tensors, total_elems) bytes of device memory, total_elems the sum
+ *   of the n (8-byte aligned; -1 for n_tensors <= 0 or total_elems < 0), which the call neither allocates
+ *   nor keeps.
+ * The table travels in the kernels' arguments, msc_adam_clip_geometry's table_capacity entries per launch:
+ * one launch per that many tensors for the norms (none with max_norm <= 0 and norms_out NULL), then one per
+ * that many for the update, each block over `chunk` consecutive elements of one tensor. No device
+ * allocation, no synchronisation, no copy from host memory. Pointers need 4-byte alignment only: a tensor
+ * whose four buffers are 16-byte aligned takes 16-byte accesses, any other 4-byte ones, with equal results.
+ * Equal calls give equal bits.
+ * Errors (msc_last_error, nothing launched): a null desc, table, workspace or p / g / m / v of an entry with
+ * n > 0; n_tensors <= 0; n_groups <= 0; a group outside [0, n_groups); step < 1; n < 0. */
+typedef struct msc_opt_tensor {
+  float* p;
+  float* g;
+  float* m;
+  float* v;
+  int64_t n;
+  int32_t group;
+} msc_opt_tensor;
+typedef struct msc_adam_clip_desc {
+  double lr;
+  double beta1;
+  double beta2;
+  double eps;
+  double max_norm;              /* <= 0: no clip */
+  int64_t step;                 /* after the increment, >= 1 */
+  int32_t write_clipped_grads;
+} msc_adam_clip_desc;
+int64_t msc_adam_clip_workspace(int32_t n_tensors, int64_t total_elems);
+int msc_adam_clip_geometry(int32_t* chunk, int32_t* table_capacity);
+int msc_adam_clip_step(const msc_adam_clip_desc* desc, const msc_opt_tensor* tensors, int32_t n_tensors,
+                       int32_t n_groups, double* norms_out, void* workspace, msc_stream_t stream);
+
 /* Rollout action sampling (RLlib TorchDiagGaussian, rlmodules/base.py:480-557) over N rows of K:
  *   std = exp(max(log_std[n % log_std_rows][k], logstd_floor)) (one shared row, or one per agent
  *   with rows n = env * W + agent), actions = mean + std * eps (eps: standard normal draws),

@@ -910,6 +910,35 @@ int msc_ppo_loss(const msc_ppo_loss_desc* desc, const float* mean, const float* 
   return 0;
 }
 
+int64_t msc_adam_clip_workspace(int32_t n_tensors, int64_t total_elems) {
+  return n_tensors >= 1 && total_elems >= 0 ? adam_clip_workspace_bytes(n_tensors, total_elems) : -1;
+}
+
+int msc_adam_clip_geometry(int32_t* chunk, int32_t* table_capacity) {
+  if (!chunk || !table_capacity) return set_err(-1, "msc_adam_clip_geometry: null argument");
+  *chunk = adam_clip_chunk(), *table_capacity = adam_clip_table_capacity();
+  return 0;
+}
+
+int msc_adam_clip_step(const msc_adam_clip_desc* desc, const msc_opt_tensor* tensors, int32_t n_tensors,
+                       int32_t n_groups, double* norms_out, void* workspace, msc_stream_t stream) {
+  if (!desc) return set_err(-1, "msc_adam_clip_step: null desc");
+  if (!tensors || !workspace) return set_err(-1, "msc_adam_clip_step: null argument");
+  if (n_tensors <= 0 || n_groups <= 0)
+    return set_err(-1, "msc_adam_clip_step: n_tensors %d and n_groups %d must be >= 1", n_tensors, n_groups);
+  if (desc->step < 1) return set_err(-1, "msc_adam_clip_step: step %lld must be >= 1", (long long)desc->step);
+  for (int32_t i = 0; i < n_tensors; i++) {
+    const msc_opt_tensor& t = tensors[i];
+    if (t.n < 0) return set_err(-1, "msc_adam_clip_step: tensor %d has n = %lld", i, (long long)t.n);
+    if (t.group < 0 || t.group >= n_groups)
+      return set_err(-1, "msc_adam_clip_step: tensor %d: group %d outside [0, %d)", i, t.group, n_groups);
+    if (t.n > 0 && (!t.p || !t.g || !t.m || !t.v))
+      return set_err(-1, "msc_adam_clip_step: tensor %d: null p, g, m or v", i);
+  }
+  HIP_TRY(launch_adam_clip(*desc, tensors, n_tensors, n_groups, norms_out, workspace, (hipStream_t)stream));
+  return 0;
+}
+
 int msc_gaussian_sample(const float* mean, const float* log_std, int32_t log_std_rows, float logstd_floor,
                         const float* eps, int64_t n_rows, int32_t k, float* actions, float* logp, float* clipped,
                         msc_stream_t stream) {

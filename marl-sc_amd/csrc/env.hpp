@@ -335,5 +335,11 @@ int ppo_loss_rows_per_block(int32_t K);
 int64_t ppo_loss_workspace_bytes(int64_t n, int32_t K);
 hipError_t launch_ppo_loss(const PpoLossArgs& a, int accumulate, float* total, double* stats, void* workspace,
                            hipStream_t st);
+// adam_clip.hip: the per-group gradient clip and the Adam step over a host table of tensors (msc_adam_clip_step)
+int adam_clip_chunk();           // elements per block
+int adam_clip_table_capacity();  // table entries per launch
+int64_t adam_clip_workspace_bytes(int32_t n_tensors, int64_t total_elems);
+hipError_t launch_adam_clip(const msc_adam_clip_desc& d, const msc_opt_tensor* tensors, int32_t n_tensors,
+                            int32_t n_groups, double* norms_out, void* workspace, hipStream_t st);
 
 }  // namespace msc

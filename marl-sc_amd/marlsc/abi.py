@@ -106,6 +106,18 @@ class MscPpoLossDesc(C.Structure):
                 ("use_kl", C.c_int32), ("log_std_rows", C.c_int32), ("accumulate_stats", C.c_int32)]
 
 
+class MscOptTensor(C.Structure):
+    """msc_opt_tensor (include/marlsc.h): one parameter tensor of msc_adam_clip_step's host table."""
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("n", C.c_int64),
+                ("group", C.c_int32)]
+
+
+class MscAdamClipDesc(C.Structure):
+    """msc_adam_clip_desc (include/marlsc.h): the fused clip + Adam step's scalars."""
+    _fields_ = [("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
+                ("max_norm", C.c_double), ("step", C.c_int64), ("write_clipped_grads", C.c_int32)]
+
+
 def lib() -> C.CDLL:
     """Load libmarlsc.so (built by __graft_entry__.build()). Raises if it is missing."""
     global _LIB
@@ -157,6 +169,10 @@ def lib() -> C.CDLL:
     L.msc_ppo_loss_workspace.restype = C.c_int64
     L.msc_ppo_loss.argtypes = [P(MscPpoLossDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int64, C.c_int32, vp, vp,
                                vp, vp, vp, vp, vp]
+    L.msc_adam_clip_workspace.argtypes = [C.c_int32, C.c_int64]
+    L.msc_adam_clip_workspace.restype = C.c_int64
+    L.msc_adam_clip_geometry.argtypes = [ip, ip]
+    L.msc_adam_clip_step.argtypes = [P(MscAdamClipDesc), vp, C.c_int32, C.c_int32, vp, vp, vp]
     L.msc_env_set_episode_counters.argtypes = [vp, vp]
     L.msc_gaussian_sample.argtypes = [vp, vp, C.c_int32, C.c_float, vp, C.c_int64, C.c_int32, vp, vp, vp, vp]
     L.msc_mlp3_w3_layout.argtypes = [C.c_int32]
@@ -218,7 +234,8 @@ def check(rc: int) -> None:
 EXPORTED_SYMBOLS = [
     "msc_env_create", "msc_env_destroy", "msc_env_dims", "msc_env_kernel_choice", "msc_env_plan", "msc_env_set_option", "msc_env_ea_memory", "msc_env_reset", "msc_env_step", "msc_env_generate_demand", "msc_env_set_pipelining", "msc_env_set_chain_priority", "msc_env_set_episode_ahead", "msc_env_set_timing", "msc_env_read_timing", "msc_env_read_timing_ea", "msc_env_work_counters", "msc_env_obs_flat",
     "msc_env_read_state", "msc_env_state_bytes", "msc_env_save_state", "msc_env_load_state", "msc_env_check",
-    "msc_env_set_episode_counters", "msc_gae", "msc_adv_normalize", "msc_gae_grouped", "msc_adv_normalize_grouped", "msc_ppo_loss_workspace", "msc_ppo_loss", "msc_gaussian_sample", "msc_mlp3_w3_layout", "msc_mlp_plan", "msc_mlp3_relu_forward", "msc_mlp2_relu_forward",
+    "msc_env_set_episode_counters", "msc_gae", "msc_adv_normalize", "msc_gae_grouped", "msc_adv_normalize_grouped", "msc_ppo_loss_workspace", "msc_ppo_loss",
+    "msc_adam_clip_workspace", "msc_adam_clip_geometry", "msc_adam_clip_step", "msc_gaussian_sample", "msc_mlp3_w3_layout", "msc_mlp_plan", "msc_mlp3_relu_forward", "msc_mlp2_relu_forward",
     "msc_mlp3_relu_forward_sampled", "msc_mlp2_relu_forward_sampled",
     "msc_mlp_musigma_layout", "msc_mlp3_relu_musigma", "msc_mlp2_relu_musigma",
     "msc_mlp_wide_supported", "msc_mlp3_relu_wide", "msc_mlp2_relu_wide", "msc_mlp3_relu_multi", "msc_mlp2_relu_multi",

@@ -52,6 +52,7 @@ import torch.nn as nn
 
 from . import dist as mdist
 from . import mlp as mlp3
+from .optim import FusedClipAdam, fused_opt_default
 from .ppo_loss import STAT_KEYS, fused_loss_default, fused_ppo_loss
 from .rollout import (LOG_STD_MIN, PolicyNets, RecurrentAPI, RolloutCollector, RolloutConfig, check_gru_config,
                       check_head_config, fused_actor_sample, gaussian_sample, head_sample, mlp_forward, network_types,
@@ -403,7 +404,8 @@ class PPOLearner:
         return float(np.mean(self.kl_coeffs))
 
     def __init__(self, module: MultiAgentActorCritic, cfg: PPOConfig, *, seed: int = 0,
-                 fused_loss: Optional[bool] = None, fused_mlp: Optional[bool] = None):
+                 fused_loss: Optional[bool] = None, fused_mlp: Optional[bool] = None,
+                 fused_opt: Optional[bool] = None):
         """fused_loss: the loss, its statistics and its gradients from the msc_ppo_loss kernel
         (marlsc/ppo_loss.py) instead of ppo_loss under autograd; None reads MSC_FUSED_LOSS (default off).
         fused_mlp: the plain MLP actors and critics (mlp.trainable: the fused inference kernels' ReLU family,
@@ -411,7 +413,11 @@ class PPOLearner:
         msc_mlp_relu_backward call backward -- instead of the torch layers; None reads MSC_FUSED_MLP_GRAD
         (default off). Everything else keeps the torch layers: mu/sigma-head backbones, GRU networks and
         MLP heads over a GRU trunk, wider actors. Per-agent policies make one call per policy.
-        Either switch needs the module on a CUDA device and raises RuntimeError otherwise."""
+        fused_opt: the per-policy gradient clip and the Adam step of every minibatch step as one
+        msc_adam_clip_step call over every parameter tensor (marlsc/optim.py:FusedClipAdam, which is then
+        `self.opt`, with torch.optim.Adam's state_dict format) instead of clip_grad_norm_ per policy and
+        torch.optim.Adam.step; None reads MSC_FUSED_OPT (default off). It covers every network.
+        Every switch needs the module on a CUDA device and raises RuntimeError otherwise."""
         self.module, self.cfg = module, cfg
         self.fused_loss = fused_loss_default() if fused_loss is None else bool(fused_loss)
         if self.fused_loss and next(module.parameters()).device.type != "cuda":
@@ -421,7 +427,17 @@ class PPOLearner:
         if self.fused_mlp and next(module.parameters()).device.type != "cuda":
             raise RuntimeError("PPOLearner(fused_mlp=True): the fused MLP backward is a HIP kernel and needs the module "
                                f"on a CUDA device, not {next(module.parameters()).device}")
-        self.opt = torch.optim.Adam(module.parameters(), lr=cfg.lr_at(0))
+        self.fused_opt = fused_opt_default() if fused_opt is None else bool(fused_opt)
+        if self.fused_opt:
+            if next(module.parameters()).device.type != "cuda":
+                raise RuntimeError("PPOLearner(fused_opt=True): the fused clip + Adam step is a HIP kernel and needs "
+                                   f"the module on a CUDA device, not {next(module.parameters()).device}")
+            groups = [list(pol.parameters()) for pol in module.policies]
+            if [id(p) for ps in groups for p in ps] != [id(p) for p in module.parameters()]:
+                raise RuntimeError("PPOLearner(fused_opt=True): the module holds parameters outside its policies")
+            self.opt = FusedClipAdam(groups, lr=cfg.lr_at(0))
+        else:
+            self.opt = torch.optim.Adam(module.parameters(), lr=cfg.lr_at(0))
         # RLlib keeps one adaptive KL coefficient per module
         self.kl_coeffs = [float(cfg.kl_coeff)] * len(module.policies)
         dev = next(module.parameters()).device
@@ -559,12 +575,15 @@ class PPOLearner:
             self.opt.zero_grad(set_to_none=True)
             total.backward()
             allreduce_grads([p for p in m.parameters() if p.grad is not None])
-            if cfg.grad_clip:
-                for pol in m.policies:  # each module's gradients by its own global norm
-                    ps = [p for p in pol.parameters() if p.grad is not None]
-                    if ps:
-                        torch.nn.utils.clip_grad_norm_(ps, cfg.grad_clip)
-            self.opt.step()
+            if self.fused_opt:  # the clip and the Adam step in one call (marlsc/optim.py)
+                self.opt.step(self.opt.param_groups[0]["lr"], cfg.grad_clip)
+            else:
+                if cfg.grad_clip:
+                    for pol in m.policies:  # each module's gradients by its own global norm
+                        ps = [p for p in pol.parameters() if p.grad is not None]
+                        if ps:
+                            torch.nn.utils.clip_grad_norm_(ps, cfg.grad_clip)
+                self.opt.step()
             for k, v in mstats.items():
                 acc[k] = acc.get(k, 0.0) + float(v)
             n += 1
@@ -607,12 +626,15 @@ class PPOLearner:
             self.opt.zero_grad(set_to_none=True)
             total.backward()
             allreduce_grads([p for p in m.parameters() if p.grad is not None])
-            if cfg.grad_clip:
-                for pol in m.policies:  # each module's gradients by its own global norm
-                    ps = [p for p in pol.parameters() if p.grad is not None]
-                    if ps:
-                        torch.nn.utils.clip_grad_norm_(ps, cfg.grad_clip)
-            self.opt.step()
+            if self.fused_opt:  # the clip and the Adam step in one call (marlsc/optim.py)
+                self.opt.step(self.opt.param_groups[0]["lr"], cfg.grad_clip)
+            else:
+                if cfg.grad_clip:
+                    for pol in m.policies:  # each module's gradients by its own global norm
+                        ps = [p for p in pol.parameters() if p.grad is not None]
+                        if ps:
+                            torch.nn.utils.clip_grad_norm_(ps, cfg.grad_clip)
+                self.opt.step()
             n += 1
         host = dev_stats.cpu()  # the one read of the update
         keys = ["policy_loss", "vf_loss", "entropy"] + (["mean_kl"] if cfg.use_kl_loss else []) + ["total_loss"]
@@ -734,10 +756,11 @@ class PPOTrainer:
     def __init__(self, env_config: Any, cfg: PPOConfig, *, root_seed: int = 42, n_envs: Optional[int] = None,
                  rollout_len: Optional[int] = None, device: int = 0, env_meta: Optional[Dict[str, Any]] = None,
                  eval_seed: Optional[int] = None, multi_mlp: Optional[bool] = None,
-                 fused_loss: Optional[bool] = None, fused_mlp: Optional[bool] = None):
+                 fused_loss: Optional[bool] = None, fused_mlp: Optional[bool] = None,
+                 fused_opt: Optional[bool] = None):
         """multi_mlp: passed to MultiAgentActorCritic (per-agent policies in one launch; None reads
-        MSC_MULTI_MLP). fused_loss / fused_mlp: passed to PPOLearner (None reads MSC_FUSED_LOSS /
-        MSC_FUSED_MLP_GRAD)."""
+        MSC_MULTI_MLP). fused_loss / fused_mlp / fused_opt: passed to PPOLearner (None reads
+        MSC_FUSED_LOSS / MSC_FUSED_MLP_GRAD / MSC_FUSED_OPT)."""
         from .seeding import SeedManager
         from .spec import EnvSpec
         from .vec_env import VecInventoryEnv
@@ -780,7 +803,7 @@ class PPOTrainer:
             for p in self.module.parameters():
                 dist.broadcast(p.data, src=0)
         self.learner = PPOLearner(self.module, cfg, seed=self.train_seed + self.rank, fused_loss=fused_loss,
-                                  fused_mlp=fused_mlp)
+                                  fused_mlp=fused_mlp, fused_opt=fused_opt)
         # advantages standardised per module (RLlib's GAE connector): one group for the shared policy,
         # one per agent otherwise
         # one noise seed for every rank: the noise is keyed by global env id (msc_normal_keyed)

@@ -12,6 +12,12 @@ sharing one policy; a minibatch of 800 rows out of an 8,000-step batch (64,000 r
 Each step also runs with the fused MLP backward (msc_mlp_relu_backward, PPOLearner(fused_mlp=True), opt-in): step_mlp is
 the torch loss with the MLPs through mlp.train_forward, step_fused_mlp the fused loss with them (the intended fast
 path). A last row runs 8 per-agent policies (ippo.yaml networks) at 800 rows each, one backward call per network.
+Each of step_torch, step_fused and step_fused_mlp also runs with the fused clip + Adam step (msc_adam_clip_step,
+marlsc/optim.py:FusedClipAdam, PPOLearner(fused_opt=True), opt-in) in place of clip_grad_norm_ + torch.optim.Adam.step:
+step_torch_opt, step_fused_opt, step_fused_mlp_opt. A third split times the clip and the Adam step alone from the
+gradients a backward left (opt_torch: clip_grad_norm_ per policy + Adam.step, as PPOLearner.update runs them;
+opt_fused: one FusedClipAdam.step). The per-agent row's step variants without _opt clip all policies' gradients in
+one clip_grad_norm_ call, as this tool always did (the learner makes one call per policy: opt_torch does too).
 The variants are alternated in one process after a warm-up; each sample is one step between two device
 events, the device idle before the first (synchronised). Medians, the 5th .. 95th percentile and the range.
 
@@ -68,10 +74,16 @@ class Steps:
         self.dev_stats = torch.zeros(5, dtype=torch.float64, device="cuda")
         self.pol = m.policies[0]
         self.params = [p for p in self.pol.parameters()]
+        from marlsc.optim import FusedClipAdam
+        self.fopt = FusedClipAdam([list(pol.parameters()) for pol in m.policies], lr=self.learner.opt.param_groups[0]["lr"])
+        self.fused_opt = False
 
     def _finish(self, total):
         self.learner.opt.zero_grad(set_to_none=True)
         total.backward()
+        if self.fused_opt:
+            self.fopt.step(self.fopt.param_groups[0]["lr"], self.cfg.grad_clip)
+            return
         if self.cfg.grad_clip:
             torch.nn.utils.clip_grad_norm_([p for p in self.params if p.grad is not None], self.cfg.grad_clip)
         self.learner.opt.step()
@@ -85,6 +97,33 @@ class Steps:
             finally:
                 self.learner.fused_mlp = False
         return run
+
+    def with_opt(self, fn):
+        """fn with the fused clip + Adam step in place of clip_grad_norm_ + torch.optim.Adam.step"""
+        def run():
+            self.fused_opt = True
+            try:
+                return fn()
+            finally:
+                self.fused_opt = False
+        return run
+
+    def opt_torch(self):
+        """the clip and the Adam step of PPOLearner.update on the gradients in place"""
+        if self.cfg.grad_clip:
+            for pol in self.m.policies:
+                torch.nn.utils.clip_grad_norm_([p for p in pol.parameters() if p.grad is not None], self.cfg.grad_clip)
+        self.learner.opt.step()
+
+    def opt_fused(self):
+        self.fopt.step(self.fopt.param_groups[0]["lr"], self.cfg.grad_clip)
+
+    def step_variants(self):
+        v = {"step_torch": self.torch_step, "step_fused": self.fused_step, "step_mlp": self.with_mlp(self.torch_step),
+             "step_fused_mlp": self.with_mlp(self.fused_step)}
+        v.update({"step_torch_opt": self.with_opt(self.torch_step), "step_fused_opt": self.with_opt(self.fused_step),
+                  "step_fused_mlp_opt": self.with_opt(self.with_mlp(self.fused_step))})
+        return v
 
     def torch_step(self):
         from marlsc.ppo import ppo_loss
@@ -164,6 +203,18 @@ def _time(variants, rounds, warmup):
     return {k: np.asarray(v) for k, v in times.items()}
 
 
+def _opt_lines(res, lines):
+    """Every step variant over the same variant with the fused clip + Adam step, and whether the fused one's p95 is
+    below the parent's p05 (the bar for turning the switch on by default)."""
+    for base in ("step_torch", "step_fused", "step_fused_mlp"):
+        k = base + "_opt"
+        res[f"{base}_over_{k}"] = res[base]["median_us"] / res[k]["median_us"]
+        clear = res[k]["p95_us"] < res[base]["p05_us"]
+        res[f"{k}_p95_below_{base}_p05"] = bool(clear)
+        lines.append(f"  {base} / {k} = {res[f'{base}_over_{k}']:.3f}   ({k} p95 {res[k]['p95_us']:.1f} "
+                     f"{'<' if clear else '>='} {base} p05 {res[base]['p05_us']:.1f})")
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=100)
@@ -190,23 +241,24 @@ def main() -> int:
             cfg, m, obs, batch = _setup(name, S, W, L, K)
             st = Steps(cfg, m, obs, batch, torch.randperm(S * W, device="cuda")[:rows])
             leaves = st.outputs()
-            t = _time({"step_torch": st.torch_step, "step_fused": st.fused_step, "step_mlp": st.with_mlp(st.torch_step),
-                       "step_fused_mlp": st.with_mlp(st.fused_step)}, rounds, args.warmup)
+            t = _time(st.step_variants(), rounds, args.warmup)
             t.update(_time({"loss_torch": lambda: st.torch_loss(leaves), "loss_fused": lambda: st.fused_loss(leaves)},
                            rounds, args.warmup))
+            t.update(_time({"opt_torch": st.opt_torch, "opt_fused": st.opt_fused}, rounds, args.warmup))
             res = {"config": name, "rows": rows, "rounds": rounds}
             lines.append(f"{name}.yaml networks, minibatch of {rows} rows (batch {S * W} rows), {rounds} rounds")
             for k, v in t.items():
                 res[k] = {"median_us": float(np.median(v)), "p05_us": float(np.percentile(v, 5)),
                           "p95_us": float(np.percentile(v, 95)), "min_us": float(v.min()), "max_us": float(v.max())}
-                lines.append(f"  {k:14s} median {res[k]['median_us']:9.1f}   p05 {res[k]['p05_us']:9.1f}   p95 "
+                lines.append(f"  {k:18s} median {res[k]['median_us']:9.1f}   p05 {res[k]['p05_us']:9.1f}   p95 "
                              f"{res[k]['p95_us']:9.1f}   range {res[k]['min_us']:.1f} .. {res[k]['max_us']:.1f}")
-            for kind in ("step", "loss"):
+            for kind in ("step", "loss", "opt"):
                 res[f"{kind}_torch_over_fused"] = res[f"{kind}_torch"]["median_us"] / res[f"{kind}_fused"]["median_us"]
                 lines.append(f"  {kind}: torch / fused = {res[f'{kind}_torch_over_fused']:.3f}")
             for k, base in (("step_mlp", "step_torch"), ("step_fused_mlp", "step_fused"), ("step_fused_mlp", "step_torch")):
                 res[f"{base}_over_{k}"] = res[base]["median_us"] / res[k]["median_us"]
                 lines.append(f"  {base} / {k} = {res[f'{base}_over_{k}']:.3f}")
+            _opt_lines(res, lines)
             results.append(res)
             del st, leaves, cfg, m, obs, batch
             torch.cuda.empty_cache()
@@ -214,18 +266,21 @@ def main() -> int:
     cfg, m, obs, batch = _setup("ippo", 8000, W, L, K, shared=False)
     idx = [torch.randperm(8000, device="cuda")[:800] * W + w for w in range(W)]
     st = AgentSteps(cfg, m, obs, batch, idx)
-    t = _time({"step_torch": st.torch_step, "step_fused": st.fused_step, "step_mlp": st.with_mlp(st.torch_step),
-               "step_fused_mlp": st.with_mlp(st.fused_step)}, args.rounds, args.warmup)
+    t = _time(st.step_variants(), args.rounds, args.warmup)
+    t.update(_time({"opt_torch": st.opt_torch, "opt_fused": st.opt_fused}, args.rounds, args.warmup))
     res = {"config": "ippo per-agent", "rows": 800, "policies": W, "rounds": args.rounds}
     lines.append(f"ippo.yaml networks, {W} per-agent policies, minibatches of 800 rows each, {args.rounds} rounds")
     for k, v in t.items():
         res[k] = {"median_us": float(np.median(v)), "p05_us": float(np.percentile(v, 5)),
                   "p95_us": float(np.percentile(v, 95)), "min_us": float(v.min()), "max_us": float(v.max())}
-        lines.append(f"  {k:14s} median {res[k]['median_us']:9.1f}   p05 {res[k]['p05_us']:9.1f}   p95 "
+        lines.append(f"  {k:18s} median {res[k]['median_us']:9.1f}   p05 {res[k]['p05_us']:9.1f}   p95 "
                      f"{res[k]['p95_us']:9.1f}   range {res[k]['min_us']:.1f} .. {res[k]['max_us']:.1f}")
     for k, base in (("step_mlp", "step_torch"), ("step_fused_mlp", "step_fused"), ("step_fused_mlp", "step_torch")):
         res[f"{base}_over_{k}"] = res[base]["median_us"] / res[k]["median_us"]
         lines.append(f"  {base} / {k} = {res[f'{base}_over_{k}']:.3f}")
+    res["opt_torch_over_fused"] = res["opt_torch"]["median_us"] / res["opt_fused"]["median_us"]
+    lines.append(f"  opt: torch / fused = {res['opt_torch_over_fused']:.3f}")
+    _opt_lines(res, lines)
     results.append(res)
     text = "\n".join(lines) + "\n"
     print(text)
