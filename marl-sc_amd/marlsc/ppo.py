@@ -396,6 +396,56 @@ def minibatch_rows(cfg: "PPOConfig", world: int = 1) -> int:
     return max(1, mb // max(1, int(world)))
 
 
+# The statistics seam of PPOLearner.minibatch_step: loss(j, ...) is module j's loss on rows idx of the flat
+# batch, end_step() closes a minibatch step, result(n) gives (the means over n steps, every module's KL sum).
+class _HostStats:
+    """ppo_loss under autograd; the statistics are added up per key on the device and read on the host every
+    step (the KL before the backward, the others after the optimizer step)."""
+
+    def __init__(self, cfg: PPOConfig, n_modules: int):
+        self.cfg, self.n_modules = cfg, n_modules
+        self.acc: Dict[str, float] = {}
+        self.kl_sum = [0.0] * n_modules
+        self.mstats: Dict[str, torch.Tensor] = {}
+
+    def loss(self, j, mean, log_std, values, flat, idx, kl_coeff):
+        loss, sts = ppo_loss(self.cfg, mean, log_std, values, {k: v[idx] for k, v in flat.items()}, kl_coeff)
+        if "mean_kl" in sts:
+            self.kl_sum[j] += float(sts["mean_kl"].detach())
+        for k, v in sts.items():
+            self.mstats[k] = self.mstats.get(k, 0.0) + v.detach() / self.n_modules
+        return loss
+
+    def end_step(self) -> None:
+        for k, v in self.mstats.items():
+            self.acc[k] = self.acc.get(k, 0.0) + float(v)
+        self.mstats = {}
+
+    def result(self, n: int):
+        return {k: v / max(n, 1) for k, v in self.acc.items()}, self.kl_sum
+
+
+class _DeviceStats:
+    """fused_ppo_loss: the kernel gathers rows idx itself and adds every module's statistics (its KL sum among
+    them) to one device f64 buffer [modules, len(STAT_KEYS)], which the host reads once, in result()."""
+
+    def __init__(self, cfg: PPOConfig, n_modules: int, device):
+        self.cfg, self.n_modules = cfg, n_modules
+        self.dev = torch.zeros((n_modules, len(STAT_KEYS)), dtype=torch.float64, device=device)
+
+    def loss(self, j, mean, log_std, values, flat, idx, kl_coeff):
+        return fused_ppo_loss(self.cfg, mean, log_std, values, flat, idx, kl_coeff, stats=self.dev[j])[0]
+
+    def end_step(self) -> None:
+        pass
+
+    def result(self, n: int):
+        host = self.dev.cpu()  # the one read of the update
+        keys = ["policy_loss", "vf_loss", "entropy"] + (["mean_kl"] if self.cfg.use_kl_loss else []) + ["total_loss"]
+        out = {k: float(host[:, STAT_KEYS.index(k)].sum()) / self.n_modules / max(n, 1) for k in keys}
+        return out, [float(x) for x in host[:, STAT_KEYS.index("mean_kl")]]
+
+
 class PPOLearner:
     """Minibatch SGD over one collected batch, module by module as RLlib's learner does."""
 
@@ -415,23 +465,21 @@ class PPOLearner:
         MLP heads over a GRU trunk, wider actors. Per-agent policies make one call per policy.
         fused_opt: the per-policy gradient clip and the Adam step of every minibatch step as one
         msc_adam_clip_step call over every parameter tensor (marlsc/optim.py:FusedClipAdam, which is then
-        `self.opt`, with torch.optim.Adam's state_dict format) instead of clip_grad_norm_ per policy and
-        torch.optim.Adam.step; None reads MSC_FUSED_OPT (default off). It covers every network.
+        `self.opt`, with torch.optim.Adam's state_dict format) instead of torch's norm clip per policy and
+        torch.optim.Adam.step (clip_and_step); None reads MSC_FUSED_OPT (default off). It covers every network.
         Every switch needs the module on a CUDA device and raises RuntimeError otherwise."""
         self.module, self.cfg = module, cfg
         self.fused_loss = fused_loss_default() if fused_loss is None else bool(fused_loss)
-        if self.fused_loss and next(module.parameters()).device.type != "cuda":
-            raise RuntimeError("PPOLearner(fused_loss=True): the fused PPO loss is a HIP kernel and needs the module "
-                               f"on a CUDA device, not {next(module.parameters()).device}")
         self.fused_mlp = mlp3.fused_mlp_default() if fused_mlp is None else bool(fused_mlp)
-        if self.fused_mlp and next(module.parameters()).device.type != "cuda":
-            raise RuntimeError("PPOLearner(fused_mlp=True): the fused MLP backward is a HIP kernel and needs the module "
-                               f"on a CUDA device, not {next(module.parameters()).device}")
         self.fused_opt = fused_opt_default() if fused_opt is None else bool(fused_opt)
+        dev = next(module.parameters()).device
+        for on, switch, kernel in ((self.fused_loss, "fused_loss", "fused PPO loss"),
+                                   (self.fused_mlp, "fused_mlp", "fused MLP backward"),
+                                   (self.fused_opt, "fused_opt", "fused clip + Adam step")):
+            if on and dev.type != "cuda":
+                raise RuntimeError(f"PPOLearner({switch}=True): the {kernel} is a HIP kernel and needs the module "
+                                   f"on a CUDA device, not {dev}")
         if self.fused_opt:
-            if next(module.parameters()).device.type != "cuda":
-                raise RuntimeError("PPOLearner(fused_opt=True): the fused clip + Adam step is a HIP kernel and needs "
-                                   f"the module on a CUDA device, not {next(module.parameters()).device}")
             groups = [list(pol.parameters()) for pol in module.policies]
             if [id(p) for ps in groups for p in ps] != [id(p) for p in module.parameters()]:
                 raise RuntimeError("PPOLearner(fused_opt=True): the module holds parameters outside its policies")
@@ -440,7 +488,6 @@ class PPOLearner:
             self.opt = torch.optim.Adam(module.parameters(), lr=cfg.lr_at(0))
         # RLlib keeps one adaptive KL coefficient per module
         self.kl_coeffs = [float(cfg.kl_coeff)] * len(module.policies)
-        dev = next(module.parameters()).device
         self.gen = torch.Generator(device=dev).manual_seed(int(seed))
         self.world = dist.get_world_size() if (dist.is_available() and dist.is_initialized()) else 1
 
@@ -550,46 +597,12 @@ class PPOLearner:
         else:
             streams = [_CyclicRows(r, min(mb, r.numel()), self.gen) for r in self._module_rows(S, W, obs.device)]
         self.last_minibatch_sizes = [st.mb for st in streams]
-        if self.fused_loss:
-            return self._update_fused(obs, seq, flat, streams)
-        acc: Dict[str, float] = {}
-        kl_sum = [0.0] * len(streams)
+        stats = self.new_stats(obs.device)
         n = 0
         while min(st.covered for st in streams) < max(1, int(cfg.num_epochs)):
-            total = None
-            mstats: Dict[str, torch.Tensor] = {}
-            for j, (pol, st) in enumerate(zip(m.policies, streams)):
-                idx = st.next()
-                if seq is not None:
-                    mean, log_std, values, idx = self._seq_forward(pol, obs, seq, idx)
-                    b = {k: v[idx] for k, v in flat.items()}
-                else:
-                    b = {k: v[idx] for k, v in flat.items()}
-                    mean, log_std, values = self._forward(pol, obs, idx)
-                loss, sts = ppo_loss(cfg, mean, log_std, values, b, self.kl_coeffs[j])
-                total = loss if total is None else total + loss
-                if "mean_kl" in sts:
-                    kl_sum[j] += float(sts["mean_kl"].detach())
-                for k, v in sts.items():
-                    mstats[k] = mstats.get(k, 0.0) + v.detach() / len(streams)
-            self.opt.zero_grad(set_to_none=True)
-            total.backward()
-            allreduce_grads([p for p in m.parameters() if p.grad is not None])
-            if self.fused_opt:  # the clip and the Adam step in one call (marlsc/optim.py)
-                self.opt.step(self.opt.param_groups[0]["lr"], cfg.grad_clip)
-            else:
-                if cfg.grad_clip:
-                    for pol in m.policies:  # each module's gradients by its own global norm
-                        ps = [p for p in pol.parameters() if p.grad is not None]
-                        if ps:
-                            torch.nn.utils.clip_grad_norm_(ps, cfg.grad_clip)
-                self.opt.step()
-            for k, v in mstats.items():
-                acc[k] = acc.get(k, 0.0) + float(v)
+            self.minibatch_step(obs, seq, flat, [st.next() for st in streams], stats)
             n += 1
-        out = {k: v / max(n, 1) for k, v in acc.items()}
-        # (this tail -- step count, KL all-reduce, adaptive coefficient, learning rate -- has a twin in
-        # _finish_update for the fused path; the default path keeps its own lines: change both together)
+        out, kl_sum = stats.result(n)
         out["num_minibatch_steps"] = n
         if cfg.use_kl_loss:  # RLlib's adaptive KL coefficient, per module
             if self.world > 1:  # the ranks' mean KL: every rank keeps the same coefficients
@@ -606,61 +619,42 @@ class PPOLearner:
         out["learning_rate"] = self.opt.param_groups[0]["lr"]
         return out
 
-    def _update_fused(self, obs: torch.Tensor, seq, flat: Dict[str, torch.Tensor], streams) -> Dict[str, float]:
-        """update()'s minibatch loop with the fused loss: the kernel gathers rows `idx` of the flat batch
-        columns itself, and every module's statistics (its KL sum among them) add up in one device f64
-        buffer [modules, 5] that the host reads once, after the last step."""
-        cfg, m = self.cfg, self.module
-        dev_stats = torch.zeros((len(streams), len(STAT_KEYS)), dtype=torch.float64, device=obs.device)
-        n = 0
-        while min(st.covered for st in streams) < max(1, int(cfg.num_epochs)):
-            total = None
-            for j, (pol, st) in enumerate(zip(m.policies, streams)):
-                idx = st.next()
-                if seq is not None:
-                    mean, log_std, values, idx = self._seq_forward(pol, obs, seq, idx)
-                else:
-                    mean, log_std, values = self._forward(pol, obs, idx)
-                loss, _ = fused_ppo_loss(cfg, mean, log_std, values, flat, idx, self.kl_coeffs[j], stats=dev_stats[j])
-                total = loss if total is None else total + loss
-            self.opt.zero_grad(set_to_none=True)
-            total.backward()
-            allreduce_grads([p for p in m.parameters() if p.grad is not None])
-            if self.fused_opt:  # the clip and the Adam step in one call (marlsc/optim.py)
-                self.opt.step(self.opt.param_groups[0]["lr"], cfg.grad_clip)
-            else:
-                if cfg.grad_clip:
-                    for pol in m.policies:  # each module's gradients by its own global norm
-                        ps = [p for p in pol.parameters() if p.grad is not None]
-                        if ps:
-                            torch.nn.utils.clip_grad_norm_(ps, cfg.grad_clip)
-                self.opt.step()
-            n += 1
-        host = dev_stats.cpu()  # the one read of the update
-        keys = ["policy_loss", "vf_loss", "entropy"] + (["mean_kl"] if cfg.use_kl_loss else []) + ["total_loss"]
-        out = {k: float(host[:, STAT_KEYS.index(k)].sum()) / len(streams) / max(n, 1) for k in keys}
-        return self._finish_update(out, n, [float(x) for x in host[:, STAT_KEYS.index("mean_kl")]], obs.device)
+    def new_stats(self, device):
+        """A fresh statistics accumulator for minibatch_step: on the device with the fused loss, else on the host."""
+        n_modules = len(self.module.policies)
+        return _DeviceStats(self.cfg, n_modules, device) if self.fused_loss else _HostStats(self.cfg, n_modules)
 
-    def _finish_update(self, out: Dict[str, float], n: int, kl_sum: List[float], device) -> Dict[str, float]:
-        """The tail of update() for the fused path: step count, RLlib's adaptive KL coefficient per module,
-        learning rate. It restates update()'s own last lines, which stay where they are so that the
-        default path is untouched: change both together."""
-        cfg = self.cfg
-        out["num_minibatch_steps"] = n
-        if cfg.use_kl_loss:
-            if self.world > 1:  # the ranks' mean KL: every rank keeps the same coefficients
-                t = torch.tensor(kl_sum, dtype=torch.float64, device=device)
-                dist.all_reduce(t, op=dist.ReduceOp.SUM)
-                kl_sum = [float(x) / self.world for x in t.tolist()]
-            for j in range(len(kl_sum)):
-                kl = kl_sum[j] / max(n, 1)
-                if kl > 2.0 * cfg.kl_target:
-                    self.kl_coeffs[j] *= 1.5
-                elif kl < 0.5 * cfg.kl_target:
-                    self.kl_coeffs[j] *= 0.5
-            out["kl_coeff"] = float(np.mean(self.kl_coeffs))
-        out["learning_rate"] = self.opt.param_groups[0]["lr"]
-        return out
+    def minibatch_step(self, obs: torch.Tensor, seq: Optional[Dict[str, Any]], flat: Dict[str, torch.Tensor],
+                       rows: Sequence[torch.Tensor], stats) -> None:
+        """One optimizer step over every module at once: rows[j] are policy j's flat row ids of obs [S, W, L] and
+        the flat batch columns (sequence ids when seq is given); the sum of the module losses, backward, the
+        gradient all-reduce, clip and step. The losses go through `stats` (new_stats), which adds up their
+        statistics. It keeps nothing of update(): the same rows by hand give the same step."""
+        total = None
+        for j, (pol, idx) in enumerate(zip(self.module.policies, rows)):
+            if seq is not None:
+                mean, log_std, values, idx = self._seq_forward(pol, obs, seq, idx)
+            else:
+                mean, log_std, values = self._forward(pol, obs, idx)
+            loss = stats.loss(j, mean, log_std, values, flat, idx, self.kl_coeffs[j])
+            total = loss if total is None else total + loss
+        self.opt.zero_grad(set_to_none=True)
+        total.backward()
+        allreduce_grads([p for p in self.module.parameters() if p.grad is not None])
+        self.clip_and_step()
+        stats.end_step()
+
+    def clip_and_step(self) -> None:
+        """Every module's gradients clipped by its own global norm (cfg.grad_clip), then the Adam step."""
+        if self.fused_opt:  # both in one call (marlsc/optim.py)
+            self.opt.step(self.opt.param_groups[0]["lr"], self.cfg.grad_clip)
+            return
+        if self.cfg.grad_clip:
+            for pol in self.module.policies:
+                ps = [p for p in pol.parameters() if p.grad is not None]
+                if ps:
+                    torch.nn.utils.clip_grad_norm_(ps, self.cfg.grad_clip)
+        self.opt.step()
 
 
 # ----------------------------------------------------------------------------------------------

@@ -341,3 +341,66 @@ def test_grouped_advantage_standardisation_restatement():
     for w in range(W):
         col = out[:, w::W]
         assert abs(col.mean()) < 1e-9 and abs(col.std() - 1.0) < 1e-9
+
+
+def _counted(obj, name, calls):
+    """obj.name wrapped so that every call appends its arguments to `calls`."""
+    fn = getattr(obj, name)
+
+    def wrapped(*a, **k):
+        calls.append(a)
+        return fn(*a, **k)
+    setattr(obj, name, wrapped)
+
+
+@pytest.mark.parametrize("kl", [False, True])
+@pytest.mark.parametrize("shared", [True, False])
+def test_update_is_its_minibatch_steps_and_they_replay_by_hand(shared, kl):
+    # update() is a loop of minibatch_step calls, one optimizer step each, and the step holds no state of the
+    # loop: the recorded rows driven through minibatch_step of a fresh learner on a copy of the initial module
+    # give the same parameters, Adam moments and statistics, bit for bit. 37 env rows of 3 agents in
+    # minibatches of 40 // 3 = 13 rows over 3 epochs: the shared policy's 111 rows take ceil(333 / 13) = 26
+    # steps that wrap across reshuffles, each per-agent policy's 37 rows ceil(111 / 13) = 9
+    import copy
+    from marlsc.ppo import MultiAgentActorCritic, PPOLearner
+    mlp = {"type": "mlp", "config": {"hidden_sizes": [32], "activation": "relu"}}
+    cfg = _cfg("ippo", use_kl_loss=kl, hysteretic_beta=0.5, parameter_sharing=shared,
+               networks={"shared_layers": None, "actor": mlp, "critic": mlp, "use_mu_sigma_head": False})
+    cfg.batch_size, cfg.num_minibatches, cfg.num_epochs, cfg.grad_clip = 40, 3, 3, 0.5
+    W, L, K, S = 3, 7, 3, 37
+    torch.manual_seed(11)
+    m0 = MultiAgentActorCritic(W, L, L * W, K, cfg.rollout_config(), shared)
+    obs = torch.randn(S, W, L)
+    batch = {"obs": obs, "actions": torch.randn(S, W, K), "logp": torch.randn(S, W) - 3,
+             "advantages": torch.randn(S, W), "value_targets": torch.randn(S, W)}
+    if kl:
+        with torch.no_grad():
+            mean, ls = m0.dist_inputs(obs)
+        batch["mean_old"], batch["log_std_old"] = mean + 0.05, ls.clone()
+
+    learner = PPOLearner(copy.deepcopy(m0), cfg, seed=3)
+    steps, opt_steps = [], []
+    _counted(learner, "minibatch_step", steps)
+    _counted(learner.opt, "step", opt_steps)
+    out = learner.update(batch)
+    n = out["num_minibatch_steps"]
+    assert n == (26 if shared else 9) and len(steps) == n and len(opt_steps) == n
+    assert learner.last_minibatch_sizes == [13] * (1 if shared else W)
+    assert list(out) == ["policy_loss", "vf_loss", "entropy"] + (["mean_kl"] if kl else []) + ["total_loss"] + \
+        ["num_minibatch_steps"] + (["kl_coeff"] if kl else []) + ["learning_rate"]
+
+    replay = PPOLearner(copy.deepcopy(m0), cfg, seed=99)  # (its generator draws nothing: the rows are given)
+    flat = {k: v.reshape(S * W, *v.shape[2:]) for k, v in batch.items() if k != "obs"}
+    stats = replay.new_stats(obs.device)
+    for _, seq, _, rows, _ in steps:
+        assert seq is None and len(rows) == len(m0.policies)
+        replay.minibatch_step(obs, None, flat, rows, stats)
+    for (name, p), q in zip(learner.module.named_parameters(), replay.module.parameters()):
+        assert torch.equal(p, q), name
+    sa, sb = learner.opt.state_dict()["state"], replay.opt.state_dict()["state"]
+    assert len(sa) == len(sb) == len(list(m0.parameters()))
+    for i in sa:
+        assert torch.equal(sa[i]["exp_avg"], sb[i]["exp_avg"]) and torch.equal(sa[i]["exp_avg_sq"], sb[i]["exp_avg_sq"])
+        assert float(sa[i]["step"]) == float(sb[i]["step"]) == n
+    means, _ = stats.result(n)
+    assert means == {k: out[k] for k in means} and list(means) == list(out)[:len(means)]

@@ -1,8 +1,8 @@
 """A/B of the learner's minibatch step with the torch loss (marlsc/ppo.py:ppo_loss under autograd, the default)
 and with the fused loss kernel (msc_ppo_loss, PPOLearner(fused_loss=True), opt-in):
-  step:  one minibatch step as PPOLearner.update runs it -- gather, forward, loss, backward, gradient clip,
-         Adam, and the per-step statistics (the torch path reads them on the host every step, the fused path
-         adds them up on the device);
+  step:  PPOLearner.minibatch_step itself, the step PPOLearner.update runs, on fixed rows -- gather, forward, loss,
+         backward, gradient clip, Adam, and the per-step statistics (the torch path reads them on the host every
+         step, the fused path adds them up on the device); one learner per switch combination over one module;
   loss:  the loss with its backward alone, from given network outputs to their gradients (torch: the v[idx]
          gathers, ppo_loss, backward; fused: fused_ppo_loss, backward), no statistic read on the host.
 Shapes: the reference ippo.yaml networks (actor / critic [256], local observations) and the mappo.yaml networks
@@ -15,13 +15,15 @@ path). A last row runs 8 per-agent policies (ippo.yaml networks) at 800 rows eac
 Each of step_torch, step_fused and step_fused_mlp also runs with the fused clip + Adam step (msc_adam_clip_step,
 marlsc/optim.py:FusedClipAdam, PPOLearner(fused_opt=True), opt-in) in place of clip_grad_norm_ + torch.optim.Adam.step:
 step_torch_opt, step_fused_opt, step_fused_mlp_opt. A third split times the clip and the Adam step alone from the
-gradients a backward left (opt_torch: clip_grad_norm_ per policy + Adam.step, as PPOLearner.update runs them;
-opt_fused: one FusedClipAdam.step). The per-agent row's step variants without _opt clip all policies' gradients in
-one clip_grad_norm_ call, as this tool always did (the learner makes one call per policy: opt_torch does too).
+gradients a backward left, through the learner's own clip_and_step (opt_torch: clip_grad_norm_ per policy +
+Adam.step; opt_fused: one FusedClipAdam.step). The per-agent row's step_torch / step_fused / step_mlp /
+step_fused_mlp clip per policy, as the learner does: they are not comparable with the same rows of
+profiles/{ppo_loss,mlp_backward,adam_clip}/ab_learner.txt, which a hand-written step with one clip_grad_norm_
+call over all policies produced (profiles/learner_loop/ab_learner.txt is the first record of this step).
 The variants are alternated in one process after a warm-up; each sample is one step between two device
 events, the device idle before the first (synchronised). Medians, the 5th .. 95th percentile and the range.
 
-  python tools/ab_learner.py [--rounds 100] [--rounds-large 20] [--warmup 10] [--out profiles/ppo_loss/ab_learner.txt]
+  python tools/ab_learner.py [--rounds 100] [--rounds-large 20] [--warmup 10] [--out profiles/learner_loop/ab_learner.txt]
   python tools/ab_learner.py --count-launches   # a few steps of each variant at 800 rows, for a kernel trace"""
 import argparse
 import json
@@ -62,128 +64,49 @@ def _setup(name: str, S: int, W: int, L: int, K: int, shared: bool = True):
     return cfg, m, obs, batch
 
 
-class Steps:
-    """The two minibatch steps of PPOLearner.update / _update_fused, one module, on fixed rows idx."""
+# the step variants: name -> (fused_loss, fused_mlp, fused_opt) of the PPOLearner that runs them
+SWITCHES = {"step_torch": (False, False, False), "step_fused": (True, False, False), "step_mlp": (False, True, False),
+            "step_fused_mlp": (True, True, False), "step_torch_opt": (False, False, True),
+            "step_fused_opt": (True, False, True), "step_fused_mlp_opt": (True, True, True)}
 
-    def __init__(self, cfg, m, obs, batch, idx):
+
+class Steps:
+    """PPOLearner.minibatch_step on fixed rows (one index tensor per policy), one learner per switch combination
+    over the same module, each with its own optimizer and statistics accumulator."""
+
+    def __init__(self, cfg, m, obs, batch, rows):
         from marlsc.ppo import PPOLearner
-        self.cfg, self.m, self.obs, self.idx = cfg, m, obs, idx
+        self.cfg, self.obs, self.rows = cfg, obs, rows
         S, W = obs.shape[0], obs.shape[1]
         self.flat = {k: v.reshape(S * W, *v.shape[2:]) for k, v in batch.items()}
-        self.learner = PPOLearner(m, cfg, seed=0, fused_loss=False)
+        self.learners = {k: PPOLearner(m, cfg, seed=0, fused_loss=fl, fused_mlp=fm, fused_opt=fo)
+                         for k, (fl, fm, fo) in SWITCHES.items()}
+        self.stats = {k: ln.new_stats(obs.device) for k, ln in self.learners.items()}
         self.dev_stats = torch.zeros(5, dtype=torch.float64, device="cuda")
-        self.pol = m.policies[0]
-        self.params = [p for p in self.pol.parameters()]
-        from marlsc.optim import FusedClipAdam
-        self.fopt = FusedClipAdam([list(pol.parameters()) for pol in m.policies], lr=self.learner.opt.param_groups[0]["lr"])
-        self.fused_opt = False
-
-    def _finish(self, total):
-        self.learner.opt.zero_grad(set_to_none=True)
-        total.backward()
-        if self.fused_opt:
-            self.fopt.step(self.fopt.param_groups[0]["lr"], self.cfg.grad_clip)
-            return
-        if self.cfg.grad_clip:
-            torch.nn.utils.clip_grad_norm_([p for p in self.params if p.grad is not None], self.cfg.grad_clip)
-        self.learner.opt.step()
-
-    def with_mlp(self, fn):
-        """fn with the learner's fused_mlp switch on"""
-        def run():
-            self.learner.fused_mlp = True
-            try:
-                return fn()
-            finally:
-                self.learner.fused_mlp = False
-        return run
-
-    def with_opt(self, fn):
-        """fn with the fused clip + Adam step in place of clip_grad_norm_ + torch.optim.Adam.step"""
-        def run():
-            self.fused_opt = True
-            try:
-                return fn()
-            finally:
-                self.fused_opt = False
-        return run
-
-    def opt_torch(self):
-        """the clip and the Adam step of PPOLearner.update on the gradients in place"""
-        if self.cfg.grad_clip:
-            for pol in self.m.policies:
-                torch.nn.utils.clip_grad_norm_([p for p in pol.parameters() if p.grad is not None], self.cfg.grad_clip)
-        self.learner.opt.step()
-
-    def opt_fused(self):
-        self.fopt.step(self.fopt.param_groups[0]["lr"], self.cfg.grad_clip)
+        # the clip and the Adam step alone, on the gradients the last backward left in place
+        self.opt_torch = self.learners["step_torch"].clip_and_step
+        self.opt_fused = self.learners["step_torch_opt"].clip_and_step
 
     def step_variants(self):
-        v = {"step_torch": self.torch_step, "step_fused": self.fused_step, "step_mlp": self.with_mlp(self.torch_step),
-             "step_fused_mlp": self.with_mlp(self.fused_step)}
-        v.update({"step_torch_opt": self.with_opt(self.torch_step), "step_fused_opt": self.with_opt(self.fused_step),
-                  "step_fused_mlp_opt": self.with_opt(self.with_mlp(self.fused_step))})
-        return v
-
-    def torch_step(self):
-        from marlsc.ppo import ppo_loss
-        b = {k: v[self.idx] for k, v in self.flat.items()}
-        mean, log_std, values = self.learner._forward(self.pol, self.obs, self.idx)
-        loss, sts = ppo_loss(self.cfg, mean, log_std, values, b, 0.2)
-        kl = float(sts["mean_kl"].detach()) if "mean_kl" in sts else 0.0
-        mstats = {k: v.detach() for k, v in sts.items()}
-        self._finish(loss)
-        return kl + sum(float(v) for v in mstats.values())
-
-    def fused_step(self):
-        from marlsc.ppo_loss import fused_ppo_loss
-        mean, log_std, values = self.learner._forward(self.pol, self.obs, self.idx)
-        loss, _ = fused_ppo_loss(self.cfg, mean, log_std, values, self.flat, self.idx, 0.2, stats=self.dev_stats)
-        self._finish(loss)
+        return {k: (lambda k=k: self.learners[k].minibatch_step(self.obs, None, self.flat, self.rows, self.stats[k]))
+                for k in SWITCHES}
 
     def outputs(self):
         with torch.no_grad():
-            mean, log_std, values = self.learner._forward(self.pol, self.obs, self.idx)
+            ln = self.learners["step_torch"]
+            mean, log_std, values = ln._forward(ln.module.policies[0], self.obs, self.rows[0])
         return [t.detach().clone().requires_grad_() for t in (mean, log_std[0], values)]
 
-    def torch_loss(self, leaves):
+    def loss_torch(self, leaves):
         from marlsc.ppo import ppo_loss
         mean, ls, values = leaves
-        b = {k: v[self.idx] for k, v in self.flat.items()}
+        b = {k: v[self.rows[0]] for k, v in self.flat.items()}
         ppo_loss(self.cfg, mean, ls.expand_as(mean), values, b, 0.2)[0].backward()
 
-    def fused_loss(self, leaves):
+    def loss_fused(self, leaves):
         from marlsc.ppo_loss import fused_ppo_loss
         mean, ls, values = leaves
-        fused_ppo_loss(self.cfg, mean, ls, values, self.flat, self.idx, 0.2, stats=self.dev_stats)[0].backward()
-
-
-class AgentSteps(Steps):
-    """The same steps over W per-agent policies: every policy's rows idx[w], one optimizer step."""
-
-    def __init__(self, cfg, m, obs, batch, idx):
-        super().__init__(cfg, m, obs, batch, idx)
-        self.params = [p for p in m.parameters()]
-
-    def torch_step(self):
-        from marlsc.ppo import ppo_loss
-        total, host = None, 0.0
-        for pol, idx in zip(self.m.policies, self.idx):
-            b = {k: v[idx] for k, v in self.flat.items()}
-            loss, sts = ppo_loss(self.cfg, *self.learner._forward(pol, self.obs, idx), b, 0.2)
-            host += sum(float(v.detach()) for v in sts.values())
-            total = loss if total is None else total + loss
-        self._finish(total)
-        return host
-
-    def fused_step(self):
-        from marlsc.ppo_loss import fused_ppo_loss
-        total = None
-        for pol, idx in zip(self.m.policies, self.idx):
-            loss, _ = fused_ppo_loss(self.cfg, *self.learner._forward(pol, self.obs, idx), self.flat, idx, 0.2,
-                                     stats=self.dev_stats)
-            total = loss if total is None else total + loss
-        self._finish(total)
+        fused_ppo_loss(self.cfg, mean, ls, values, self.flat, self.rows[0], 0.2, stats=self.dev_stats)[0].backward()
 
 
 def _time(variants, rounds, warmup):
@@ -227,8 +150,8 @@ def main() -> int:
     W, K, L = 8, 5, _local_obs_dim()
     if args.count_launches:
         cfg, m, obs, batch = _setup("ippo", 8000, W, L, K)
-        st = Steps(cfg, m, obs, batch, torch.randperm(8000 * W, device="cuda")[:800])
-        for fn in (st.torch_step, st.fused_step):
+        st = Steps(cfg, m, obs, batch, [torch.randperm(8000 * W, device="cuda")[:800]])
+        for fn in (st.step_variants()[k] for k in ("step_torch", "step_fused")):
             for _ in range(10):
                 fn()
             torch.cuda.synchronize()
@@ -239,10 +162,10 @@ def main() -> int:
     for name in ("ippo", "mappo"):
         for S, rows, rounds in ((8000, 800, args.rounds), (32768, 32768 * W, args.rounds_large)):
             cfg, m, obs, batch = _setup(name, S, W, L, K)
-            st = Steps(cfg, m, obs, batch, torch.randperm(S * W, device="cuda")[:rows])
+            st = Steps(cfg, m, obs, batch, [torch.randperm(S * W, device="cuda")[:rows]])
             leaves = st.outputs()
             t = _time(st.step_variants(), rounds, args.warmup)
-            t.update(_time({"loss_torch": lambda: st.torch_loss(leaves), "loss_fused": lambda: st.fused_loss(leaves)},
+            t.update(_time({"loss_torch": lambda: st.loss_torch(leaves), "loss_fused": lambda: st.loss_fused(leaves)},
                            rounds, args.warmup))
             t.update(_time({"opt_torch": st.opt_torch, "opt_fused": st.opt_fused}, rounds, args.warmup))
             res = {"config": name, "rows": rows, "rounds": rounds}
@@ -265,7 +188,7 @@ def main() -> int:
     # per-agent policies: 8 ippo.yaml policies, 800 rows each out of each agent's 8,000
     cfg, m, obs, batch = _setup("ippo", 8000, W, L, K, shared=False)
     idx = [torch.randperm(8000, device="cuda")[:800] * W + w for w in range(W)]
-    st = AgentSteps(cfg, m, obs, batch, idx)
+    st = Steps(cfg, m, obs, batch, idx)
     t = _time(st.step_variants(), args.rounds, args.warmup)
     t.update(_time({"opt_torch": st.opt_torch, "opt_fused": st.opt_fused}, args.rounds, args.warmup))
     res = {"config": "ippo per-agent", "rows": 800, "policies": W, "rounds": args.rounds}
