@@ -366,7 +366,8 @@ __global__ __launch_bounds__(64) void alloc_lane_kernel(const DevEnv* __restrict
       if (LPE == 1 && cand == 0u) {
         open = false;
       } else {
-      // cheapest candidate, lowest index on ties (the stable argsort order the fixtures assert)
+      // cheapest candidate, lowest index on ties (the stable argsort order, asserted on costs that
+      // tie by tests/test_gpu_alloc_ties.py)
       double best = INFINITY;
       int b = LPE == 1 ? 0 : SENT;
 #pragma unroll
