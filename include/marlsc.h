@@ -215,7 +215,13 @@ int msc_env_set_option(msc_env* env, int32_t key, int32_t value);
 int msc_env_reset(msc_env* env, const uint8_t* mask, const uint32_t* new_root_seeds, int32_t flags,
                   float* obs, msc_stream_t stream);
 
-/* One step of every env. actions [E][W][K] in [-1, 1]. Outputs obs [E][W][L] (local obs of
+/* One step of every env. actions [E][W][K] in [-1, 1]: they must be finite; values outside
+ * [-1, 1] are rescaled like the reference's (direct clamps to [0, max_order_quantities], the other
+ * two action types only at 0). The pending total of a warehouse, over all its SKUs and arrival
+ * slots, must stay below 2^24: the totals are integer sums here and float32 sums in the reference
+ * (order by order per SKU, numpy's pairwise sum for the observation's total), which agree while
+ * every partial sum is exact in float32, that is up to 2^24 - 1.
+ * Outputs obs [E][W][L] (local obs of
  * every agent), rewards [E][W] (f32, and optionally f64), truncated [E]. An env whose episode
  * ends is reset in the same call (RLlib's EnvRunner semantics): its terminal observation goes
  * to final_obs (if non-NULL) and obs receives the first observation of the next episode. */
