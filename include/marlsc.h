@@ -205,6 +205,15 @@ int msc_env_plan(const msc_env_desc* desc, int64_t n_envs, int32_t n_cus, int64_
 #define MSC_OPT_STEP_C_FORM 1
 #define MSC_OPT_ALLOC_PRIO_SPLIT 2
 int msc_env_set_option(msc_env* env, int32_t key, int32_t value);
+/* MSC_OPT_ALLOC_TAIL (msc_env_set_option): 1 (default) lets a one-env-per-lane allocation wave whose
+ * envs have all sold out (or run out of orders) finish its remaining orders in a short loop that
+ * only counts them as lost; 0 keeps every order on the general path. Results are bit-identical. */
+#define MSC_OPT_ALLOC_TAIL 3
+/* The order index at which each block (64 consecutive envs) of the one-env-per-lane allocation
+ * kernel entered that loop in the last step, -1 where it did not (the option off, another allocator,
+ * or some env kept stock up to the last order of the block's busiest env). Synchronizes the device;
+ * copies min(n, ceil(n_envs / 64)) values to the host array `out`. Returns 0, or < 0 on error. */
+int msc_env_alloc_tail_entry(const msc_env* env, int32_t* out, int64_t n);
 
 #define MSC_RESET_EVAL_RESTART 1  /* reset(seed=...) of a construction-seeded eval env: counter -> 0 */
 

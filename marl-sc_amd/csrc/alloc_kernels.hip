@@ -40,6 +40,13 @@ hipError_t launch_alloc_lane_k(const EnvConst& c, const DevEnv* d, const StepIO&
 #ifndef MSC_AL_PRIO2
 #define MSC_AL_PRIO2 1  // the priority after c.al_psplit 16ths of the orders: below the demand parser (2)
 #endif
+#ifndef MSC_AL_PRIO_TAIL
+#define MSC_AL_PRIO_TAIL 0  // a wave entering the sold-out tail with a split < 16: 0 keeps following the split,
+                            // 1 drops to MSC_AL_PRIO2 at once
+#endif
+#ifndef MSC_AL_TAIL_WIN
+#define MSC_AL_TAIL_WIN 0  // the sold-out test runs at every order (0) or only where a record window starts (1)
+#endif
 
 // LDS layout of one block (64 envs); word offsets
 struct AlLds {
@@ -304,7 +311,26 @@ __global__ __launch_bounds__(64) void alloc_lane_kernel(const DevEnv* __restrict
   // (msc_env_set_option MSC_OPT_ALLOC_PRIO_SPLIT; 16: all of them)
   const int aps = __builtin_amdgcn_readfirstlane(c.chain_prio ? 16 : c.al_psplit);
   const int psplit = MSC_AL_PRIO > 0 && aps < 16 ? (wmax * aps) >> 4 : -1;
-  for (int oi = 0; oi <= wmax; oi++) {
+  // The sold-out tail (LPE 1; msc_env_set_option MSC_OPT_ALLOC_TAIL). A lane is done once its stock
+  // masks are all zero or its list has ended; stock bits are only ever cleared here, so done is
+  // one-way. From then on every order of the lane has no candidate: it ships nothing, is lost unless
+  // all its quantities are zero, and its region's unfulfilled demand is its demand. Once every lane
+  // of the wave is done with orders still to go, the wave leaves this loop for the tail loop below.
+  const bool tail_on = LPE == 1 && __builtin_amdgcn_readfirstlane(c.al_tail) != 0;
+  int tail_at = -1;  // the order index at which the wave entered the tail
+  int oi = 0;
+  for (; oi <= wmax; oi++) {
+    if constexpr (LPE == 1) {
+      if (tail_on && oi < wmax && (MSC_AL_TAIL_WIN == 0 || oi % AL_CH == 0)) {
+        uint32_t any = 0u;
+#pragma unroll
+        for (int sk = 0; sk < K; sk++) any |= stock[sk];
+        if (__builtin_amdgcn_ballot_w64(any != 0u && oi < n_orders) == 0ull) {  // (scalar branch)
+          tail_at = oi;
+          break;
+        }
+      }
+    }
     if (oi == psplit) __builtin_amdgcn_s_setprio(MSC_AL_PRIO2);
     const int jw = oi % AL_CH;
     if (jw == 0 && oi > 0) {  // wave-uniform: window oi / AL_CH is due, start the one after
@@ -470,6 +496,58 @@ __global__ __launch_bounds__(64) void alloc_lane_kernel(const DevEnv* __restrict
     }
     lost_cnt += remor != 0 ? 1 : 0;
     }
+  }
+
+  if constexpr (LPE == 1) {
+    if (tail_at >= 0) {
+      // The tail loop: the same record windows, closing iteration (oi == wmax) and priority split,
+      // and per order only what the result still needs -- the region's demand, its unfulfilled
+      // demand (all of it) and the lost-order count. Penalties still accumulate region by region,
+      // so every f64 sum keeps its order.
+      if (MSC_AL_PRIO_TAIL != 0 && oi < psplit) __builtin_amdgcn_s_setprio(MSC_AL_PRIO2);
+      for (; oi <= wmax; oi++) {
+        if (MSC_AL_PRIO_TAIL == 0 && oi == psplit) __builtin_amdgcn_s_setprio(MSC_AL_PRIO2);
+        const int jw = oi % AL_CH;
+        if (jw == 0 && oi > 0) {
+          publish();
+          fetch(oi / AL_CH + 1);
+        }
+        union {
+          uint4 v[NVR];
+          uint16_t h[8 * NVR];
+        } ur;
+#pragma unroll
+        for (int v = 0; v < NVR; v++) ur.v[v] = Lrec[(jw * NVR + v) * 64];
+        const int r = oi < n_orders ? (int)ur.h[0] : -1;
+        if (r != cur) {
+          // The region open at the switch may have shipments (smask, rtot, shc, Lqs): the epilogue
+          // as ever. A region that begins here gets none: with rtot 0 its penalty goes to the
+          // closest warehouse (or through the softmax), with smask 0 no Lqs row is cleared, and with
+          // hw -1 no shipped-home value is stored (the prologue's zeros stand; SH: the LDS table).
+          if (cur >= 0) finalize(cur);
+          cur = r;
+          lost_cnt = 0;
+#pragma unroll
+          for (int sk = 0; sk < K; sk++) u[sk] = dsum[sk] = 0;
+          hm = r >= 0 ? Lhm[r] : 0u;
+          hw = -1;
+          smask = 0u;
+          rtot = 0;
+        }
+        if (oi < n_orders) {
+          int dor = 0;
+#pragma unroll
+          for (int sk = 0; sk < K; sk++) {
+            const int dq = ur.h[1 + sk];
+            dsum[sk] += dq;
+            u[sk] += dq;
+            dor |= dq;
+          }
+          lost_cnt += dor != 0 ? 1 : 0;
+        }
+      }
+    }
+    if (lane == 0) s.al_tail[blockIdx.x] = tail_at;  // (msc_env_alloc_tail_entry)
   }
 
   if (!ev) return;

@@ -49,6 +49,7 @@ struct msc_env {
   void* scratch = nullptr;    // two per-step order buffers (double-buffered for pipelining)
   size_t order_bytes = 0;     // bytes of one order buffer (records + counts)
   DevEnv* dev = nullptr;      // device copies of {c, s}: dev[b] points at order buffer b
+  void* al_tail = nullptr;    // s.al_tail: one int32 per 64 envs (msc_env_alloc_tail_entry)
   // Demand pipelining: the Poisson demand of step tau+1 depends only on each env's own demand
   // stream, so it is generated on a side stream while the step kernel of tau runs (their waves
   // co-reside on the CUs), unless step tau ends an episode (the in-kernel reset re-seeds the
@@ -121,7 +122,7 @@ static void timing_free(msc_env* env) {
 // Everything a handle owns; msc_env_destroy and a failing msc_env_create both end here (members a
 // partial create has not reached yet are null).
 static void env_release(msc_env* env) {
-  for (void* m : {env->tables, env->arena, env->scratch, (void*)env->dev, env->ea_mem})
+  for (void* m : {env->tables, env->arena, env->scratch, (void*)env->dev, env->ea_mem, env->al_tail})
     if (m) (void)hipFree(m);
   for (hipEvent_t e : {env->ev_dem[0], env->ev_dem[1], env->ev_step[0], env->ev_step[1], env->ev_reset, env->ev_snap,
                        env->ev_chunk})
@@ -335,6 +336,12 @@ int msc_env_create(const msc_env_desc* d, int device, int64_t n_envs, uint32_t b
       env->ea_mem = nullptr;
       c.ea_S = 0;
     }
+  }
+  {  // alloc_lane's tail entries, -1 until a step writes them
+    const size_t bytes = sizeof(int32_t) * (size_t)((E + BS - 1) / BS);
+    if (hipMalloc(&env->al_tail, bytes) != hipSuccess || hipMemset(env->al_tail, 0xff, bytes) != hipSuccess)
+      return fail(set_err(-2, "hipMalloc(tail entries) failed"));
+    s.al_tail = (int32_t*)env->al_tail;
   }
   EnvState s2 = s;
   if (s.orders) {
@@ -661,7 +668,27 @@ int msc_env_set_option(msc_env* env, int32_t key, int32_t value) {
       HIP_TRY(hipMemcpy(&env->dev[b].c.al_psplit, &value, sizeof value, hipMemcpyHostToDevice));
     return 0;
   }
+  if (key == MSC_OPT_ALLOC_TAIL) {
+    if (value != 0 && value != 1) return set_err(-1, "MSC_OPT_ALLOC_TAIL must be 0 or 1");
+    if (env->c.al_tail == value) return 0;
+    env->c.al_tail = value;
+    HIP_TRY(hipSetDevice(env->device));
+    HIP_TRY(hipDeviceSynchronize());  // no launch in flight reads the descriptors being patched
+    for (int b = 0; b < 2; b++)
+      HIP_TRY(hipMemcpy(&env->dev[b].c.al_tail, &value, sizeof value, hipMemcpyHostToDevice));
+    return 0;
+  }
   return set_err(-1, "unknown option %d", key);
+}
+
+int msc_env_alloc_tail_entry(const msc_env* env, int32_t* out, int64_t n) {
+  if (!env || (!out && n > 0)) return set_err(-1, "null argument");
+  const int64_t blocks = (env->c.E + BS - 1) / BS;
+  const int64_t m = n < blocks ? n : blocks;
+  HIP_TRY(hipSetDevice(env->device));
+  HIP_TRY(hipDeviceSynchronize());
+  if (m > 0) HIP_TRY(hipMemcpy(out, env->al_tail, sizeof(int32_t) * (size_t)m, hipMemcpyDeviceToHost));
+  return 0;
 }
 
 int msc_env_set_timing(msc_env* env, int32_t max_steps) {

@@ -50,6 +50,7 @@ struct EnvConst {
   int32_t sc_tab;       // alloc_scan_kernel stages the {of, ov} table in LDS (when it fits: TAB form)
   int32_t sc_form;      // step_c_kernel's 16-wave form: compiled for 5 (env stepping) or 4 (rollout) waves per SIMD
   int32_t al_psplit;    // alloc_lane: 16ths of the wave's busiest env's orders run at s_setprio 3, the rest at 1
+  int32_t al_tail;      // alloc_lane: 1 = a wave whose envs have all sold out takes the tail loop (MSC_OPT_ALLOC_TAIL)
   uint32_t flags;
   int64_t E;
   int64_t ea_cap;       // episode-ahead demand: order records per (slot, env) episode
@@ -114,6 +115,9 @@ struct EnvState {
   MSC_G int32_t* ea_off;     // [S][T + 1][E] first record of step t (off[T] = the episode's count)
   MSC_G uint32_t* ea_pos;    // [S][T][E]     demand-stream position (draws) after step t
   MSC_G int32_t* ea_cnt;     // [S][E]        SeedManager._episode_counter after the slot episode's reset
+  // outside the arena (not part of a saved state):
+  MSC_G int32_t* al_tail;    // [ceil(E / 64)] alloc_lane: the order index at which each block entered its sold-out
+                             // tail in the last step, -1 if it did not (msc_env_alloc_tail_entry)
 };
 
 // one launch of the episode-ahead demand generator: lanes (k, e) for k < nslots generate the

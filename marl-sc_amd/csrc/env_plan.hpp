@@ -342,6 +342,8 @@ inline int plan_env(const msc_env_desc* d, int64_t n_envs, int n_cus, const EnvK
   // beside 0.86); 12/16 balanced them (341 -> 349 M agent-steps/s, profiles/r06/ab_alloc_prio.txt), and
   // 14/16 does with the shorter generator draw (361 -> 368 M, profiles/gen_draw/ab_alloc_prio.txt)
   c.al_psplit = k.al_prio_split && *k.al_prio_split >= 1 && *k.al_prio_split <= 16 ? *k.al_prio_split : 14;
+  // alloc_lane's sold-out tail: on; per handle msc_env_set_option(MSC_OPT_ALLOC_TAIL, 0 | 1) (results identical)
+  c.al_tail = 1;
 
   // -- fusion
   // Phase C inside the scan allocator (one env per wave: its obs, rewards and state updates from the

@@ -214,9 +214,20 @@ class VecInventoryEnv:
     STEP_C_FORM = 1  # include/marlsc.h MSC_OPT_STEP_C_FORM
     ALLOC_PRIO_SPLIT = 2  # include/marlsc.h MSC_OPT_ALLOC_PRIO_SPLIT
 
+    ALLOC_TAIL = 3  # include/marlsc.h MSC_OPT_ALLOC_TAIL
+
     def set_option(self, key: int, value: int) -> None:
         """A kernel-form option of this handle (msc_env_set_option; results are identical)."""
         abi.check(abi.lib().msc_env_set_option(self._h, int(key), int(value)))
+
+    def alloc_tail_entry(self) -> np.ndarray:
+        """Per block of 64 envs, the order index at which the lane allocator entered its sold-out tail
+        in the last step, -1 where it did not (msc_env_alloc_tail_entry; synchronizes the device)."""
+        n = (self.n_envs + 63) // 64
+        buf = (C.c_int32 * n)()
+        with torch.cuda.device(self.device):
+            abi.check(abi.lib().msc_env_alloc_tail_entry(self._h, buf, n))
+        return np.frombuffer(buf, dtype=np.int32).copy()
 
     def kernel_choice(self) -> Dict[str, int]:
         """The kernels this handle runs (msc_env_kernel_choice), chosen at create time by shape."""
