@@ -774,6 +774,45 @@ int msc_mlp_relu_backward(const float* x, int64_t n_rows, int32_t in_dim, int32_
                           const float* w3, const float* d_out, float scale, int32_t accumulate, float* g_w1, float* g_b1,
                           float* g_w2, float* g_b2, float* g_w3, float* g_b3, void* workspace, msc_stream_t stream);
 
+/* The same gradients for the n_policies same-shaped networks of per-agent policies (parameter_sharing: false) in
+ * one call: three launches per round for a whole group of policies instead of three per policy.
+ * Layout, msc_mlp{3,2}_relu_multi's: x [n_rows][in_dim] and d_out [n_rows][out_dim] hold the rows ordered
+ * [n_rows / n_policies][n_policies], row r belongs to policy r % n_policies and is read where it lies, at stride
+ * n_policies (never gathered). w1p, b1, w2p, b2, w2tp are n_policies consecutive single-policy packs / vectors,
+ * each exactly as msc_mlp_relu_backward takes one; w3 is [n_policies][out_dim][hidden_last]. The six outputs are
+ * the stacked torch layouts g_w1 [n_policies][hidden1][in_dim], g_b1 [n_policies][hidden1], ...,
+ * g_b3 [n_policies][out_dim]. 1 <= n_policies <= 64 and n_policies divides n_rows; the shape set, the alignment
+ * rules and the NULL rules are msc_mlp_relu_backward's. A violated condition returns an error (msc_last_error)
+ * and writes nothing. n_rows = 0: zeros over all the stacked outputs (accumulate = 0) or nothing (accumulate = 1);
+ * x is not read.
+ * Contract: for every policy p, the six gradients equal, bit for bit, what msc_mlp_relu_backward returns for policy
+ * p's n_rows / n_policies rows gathered contiguously, with policy p's packs and the same scale and accumulate.
+ * Every policy keeps that call's geometry (row tiles of 32, slices, rounds, partials) in a workspace section of its
+ * own, the policy index comes from the grid, and there are no atomics; so the determinism, the integer exactness
+ * (2^24 headroom) and the mask (z > 0, the forward kernels' masks) paragraphs above hold per policy, and the result
+ * depends neither on the block order nor on the grouping below. Nothing is read or written past n_rows rows, and
+ * nothing is written past the stacked outputs or past the workspace bytes the query returned.
+ * workspace: msc_mlp_relu_backward_multi_workspace(...) bytes (-1 exactly where the single query is, or for a bad
+ * n_policies / n_rows pair) = G x msc_mlp_relu_backward_workspace(n_rows / n_policies, ...): the policies run in
+ * groups of G per set of launches, G the largest count (at least 1, at most n_policies) for which G workspaces at
+ * the single call's cap fit 1 GiB. G depends on in_dim, the hidden sizes and out_dim alone, so the bytes are
+ * monotone in n_rows and capped.
+ * msc_mlp_relu_backward_multi_plan touches no GPU: it writes up to n of
+ *  {supported (0: the call would refuse these sizes, and every other value is 0), policies per group G,
+ *   groups = ceil(n_policies / G), rounds per policy, slices per round, row tiles of a full round (of the only
+ *   round when there is one), workspace bytes}
+ * and returns the count written (MSC_MLP_BWD_MULTI_PLAN_N at most), or < 0 for a NULL out. */
+#define MSC_MLP_BWD_MULTI_PLAN_N 7
+int64_t msc_mlp_relu_backward_multi_workspace(int64_t n_rows, int32_t n_policies, int32_t in_dim, int32_t hidden1,
+                                              int32_t hidden2, int32_t out_dim);
+int msc_mlp_relu_backward_multi_plan(int64_t n_rows, int32_t n_policies, int32_t in_dim, int32_t hidden1, int32_t hidden2,
+                                     int32_t out_dim, int64_t* out, int32_t n);
+int msc_mlp_relu_backward_multi(const float* x, int64_t n_rows, int32_t n_policies, int32_t in_dim, int32_t hidden1,
+                                int32_t hidden2, int32_t out_dim, const float* w1p, const float* b1, const float* w2p,
+                                const float* b2, const float* w2tp, const float* w3, const float* d_out, float scale,
+                                int32_t accumulate, float* g_w1, float* g_b1, float* g_w2, float* g_b2, float* g_w3,
+                                float* g_b3, void* workspace, msc_stream_t stream);
+
 /* One time step of a GRU network for n_rows rows in one launch: replaces the module
  * GRUArchitecture.build returns (architectures/gru.py:14-85: nn.GRU(batch_first) -> output_proj =
  * [act,] Linear [, act]) as BaseRLModule._forward_gru steps it on a [B, obs_dim] input

@@ -1363,6 +1363,69 @@ int msc_mlp_relu_backward(const float* x, int64_t n_rows, int32_t in_dim, int32_
   return 0;
 }
 
+// the same for the P same-shaped networks of per-agent policies in one call (rows [n_rows / P][P], stacked packs
+// and outputs): per policy, bit for bit what msc_mlp_relu_backward gives for its gathered rows
+static const MlpEntry MLP_BWD_MULTI{"fused", nullptr, true, 32, true};
+
+static bool mlp_bwd_multi_shape(int64_t n_rows, int32_t n_policies, int32_t in_dim, int32_t hidden1, int32_t hidden2,
+                                int32_t out_dim) {
+  return n_policies >= 1 && n_policies <= 64 && n_rows >= 0 && n_rows % n_policies == 0 &&
+         msc_mlp_relu_backward_workspace(n_rows / n_policies, in_dim, hidden1, hidden2, out_dim) >= 0;
+}
+
+int64_t msc_mlp_relu_backward_multi_workspace(int64_t n_rows, int32_t n_policies, int32_t in_dim, int32_t hidden1,
+                                              int32_t hidden2, int32_t out_dim) {
+  if (!mlp_bwd_multi_shape(n_rows, n_policies, in_dim, hidden1, hidden2, out_dim)) return -1;
+  const MlpBwdMultiPlan p = mlp_backward_multi_plan(n_rows / n_policies, n_policies, in_dim, hidden1, hidden2, out_dim);
+  return p.G * p.policy_bytes;
+}
+
+int msc_mlp_relu_backward_multi_plan(int64_t n_rows, int32_t n_policies, int32_t in_dim, int32_t hidden1, int32_t hidden2,
+                                     int32_t out_dim, int64_t* out, int32_t n) {
+  if (!out && n > 0) return set_err(-1, "null argument");
+  int64_t v[MSC_MLP_BWD_MULTI_PLAN_N] = {0, 0, 0, 0, 0, 0, 0};
+  if (mlp_bwd_multi_shape(n_rows, n_policies, in_dim, hidden1, hidden2, out_dim)) {
+    const MlpBwdMultiPlan p = mlp_backward_multi_plan(n_rows / n_policies, n_policies, in_dim, hidden1, hidden2, out_dim);
+    const int64_t w[MSC_MLP_BWD_MULTI_PLAN_N] = {1, p.G, p.groups, p.rounds, p.nslice, p.tiles, p.G * p.policy_bytes};
+    for (int i = 0; i < MSC_MLP_BWD_MULTI_PLAN_N; i++) v[i] = w[i];
+  }
+  const int m = n < MSC_MLP_BWD_MULTI_PLAN_N ? (n < 0 ? 0 : n) : MSC_MLP_BWD_MULTI_PLAN_N;
+  for (int i = 0; i < m; i++) out[i] = v[i];
+  return m;
+}
+
+int msc_mlp_relu_backward_multi(const float* x, int64_t n_rows, int32_t n_policies, int32_t in_dim, int32_t hidden1,
+                                int32_t hidden2, int32_t out_dim, const float* w1p, const float* b1, const float* w2p,
+                                const float* b2, const float* w2tp, const float* w3, const float* d_out, float scale,
+                                int32_t accumulate, float* g_w1, float* g_b1, float* g_w2, float* g_b2, float* g_w3,
+                                float* g_b3, void* workspace, msc_stream_t stream) {
+  const bool two = hidden2 != 0;
+  if (const int r = mlp_check(MLP_BWD_MULTI, two, {x, n_rows, in_dim, hidden1, hidden2, out_dim, w1p, b1, w2p, b2, w3, d_out,
+                                                   nullptr, nullptr, n_policies}, g_w1))
+    return r;
+  if (!g_b1 || !g_w3 || !g_b3 || (two && (!w2tp || !g_w2 || !g_b2)) || (n_rows > 0 && !workspace))
+    return set_err(-1, "null argument");
+  if (((uintptr_t)w2tp | (uintptr_t)workspace) & 15) return set_err(-1, "w2tp and the workspace must be 16-byte aligned");
+  const hipStream_t st = (hipStream_t)stream;
+  const int64_t P = n_policies, HL = two ? hidden2 : hidden1;
+  if (n_rows == 0) {  // as the single call, over the P stacked outputs
+    if (accumulate) return 0;
+    HIP_TRY(hipMemsetAsync(g_w1, 0, sizeof(float) * P * hidden1 * in_dim, st));
+    HIP_TRY(hipMemsetAsync(g_b1, 0, sizeof(float) * P * hidden1, st));
+    if (two) {
+      HIP_TRY(hipMemsetAsync(g_w2, 0, sizeof(float) * P * hidden2 * hidden1, st));
+      HIP_TRY(hipMemsetAsync(g_b2, 0, sizeof(float) * P * hidden2, st));
+    }
+    HIP_TRY(hipMemsetAsync(g_w3, 0, sizeof(float) * P * out_dim * HL, st));
+    HIP_TRY(hipMemsetAsync(g_b3, 0, sizeof(float) * P * out_dim, st));
+    return 0;
+  }
+  const MlpBwdArgs a{x, n_rows / P, in_dim, hidden1, hidden2, out_dim, w1p, b1, w2p, b2, w2tp, w3, d_out, scale,
+                     accumulate ? 1 : 0, g_w1, g_b1, g_w2, g_b2, g_w3, g_b3};
+  HIP_TRY(launch_mlp_backward_multi(a, n_policies, workspace, st));
+  return 0;
+}
+
 // GRU networks (replaces GRUArchitecture's gru -> output_proj as BaseRLModule._forward_gru steps it,
 // architectures/gru.py:14-85, rlmodules/base.py:99-141)
 int msc_gru_supported(int32_t in_dim, int32_t hidden, int32_t layers, int32_t out_dim) {

@@ -204,6 +204,12 @@ def lib() -> C.CDLL:
     L.msc_mlp_relu_backward_workspace.restype = C.c_int64
     L.msc_mlp_relu_backward.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, vp,
                                         vp, C.c_float, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.msc_mlp_relu_backward_multi_workspace.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+    L.msc_mlp_relu_backward_multi_workspace.restype = C.c_int64
+    L.msc_mlp_relu_backward_multi_plan.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                   P(C.c_int64), C.c_int32]
+    L.msc_mlp_relu_backward_multi.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp,
+                                              vp, vp, vp, vp, vp, C.c_float, C.c_int32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.msc_reward_team_sum.argtypes = [vp, C.c_int64, C.c_int32, vp, vp, vp]
     L.msc_gru_supported.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     L.msc_gru_step.argtypes = [vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, P(MscGruWeights), C.c_int32,
@@ -241,6 +247,7 @@ EXPORTED_SYMBOLS = [
     "msc_mlp_musigma_layout", "msc_mlp3_relu_musigma", "msc_mlp2_relu_musigma",
     "msc_mlp_wide_supported", "msc_mlp3_relu_wide", "msc_mlp2_relu_wide", "msc_mlp3_relu_multi", "msc_mlp2_relu_multi",
     "msc_mlp_relu_backward_workspace", "msc_mlp_relu_backward",
+    "msc_mlp_relu_backward_multi_workspace", "msc_mlp_relu_backward_multi_plan", "msc_mlp_relu_backward_multi",
     "msc_reward_team_sum",
     "msc_gru_supported", "msc_gru_step",
     "msc_policy_create", "msc_policy_act", "msc_policy_set_tables", "msc_policy_destroy",

@@ -24,7 +24,9 @@ one launch each over the rows [..., W, L] (msc_mlp{2,3}_relu_multi, csrc/mlp_mul
 the end of this file; opt-in, MSC_MULTI_MLP=1).
 
 The plain MLPs can also be trained through the kernels (train_forward: the inference kernel forward, one
-msc_mlp_relu_backward call backward, csrc/mlp_backward.hip; opt-in, MSC_FUSED_MLP_GRAD=1): the last section.
+msc_mlp_relu_backward call backward, csrc/mlp_backward.hip; opt-in, MSC_FUSED_MLP_GRAD=1), and the P networks of
+per-agent policies through one call each way (multi_train_forward: multi_forward forward, one
+msc_mlp_relu_backward_multi call backward; opt-in, MSC_FUSED_MULTI_GRAD=1): the last two sections.
 
 There is no CPU fallback: a CUDA tensor on a build without libmarlsc raises (abi.lib()).
 """
@@ -708,8 +710,8 @@ def multi_forward(mods_list, x: torch.Tensor, out: Optional[torch.Tensor] = None
 # is mlp3_forward, the inference kernel, so the learner's forward equals the collector's bit for bit; the
 # backward is one msc_mlp_relu_backward call (csrc/mlp_backward.hip) that recomputes the hidden layers and
 # returns the six parameter gradients in torch's layouts. No input gradient. Not covered (they keep the torch
-# layers): mu/sigma-head backbones, GRU networks and MLP heads over a GRU trunk, the wide (33..128 outputs)
-# actor, and a multi-policy backward (per-agent policies make one call each).
+# layers): mu/sigma-head backbones, GRU networks and MLP heads over a GRU trunk, and the wide (33..128 outputs)
+# actor. Per-agent policies make one call each here; the section after this one runs them in one.
 # ----------------------------------------------------------------------------------------------
 def fused_mlp_default() -> bool:
     """MSC_FUSED_MLP_GRAD=1 turns the fused MLP backward on where PPOLearner is built with fused_mlp=None."""
@@ -826,3 +828,149 @@ def train_forward(mods, x: torch.Tensor) -> torch.Tensor:
         raise RuntimeError("train_forward: the parameters must be float32 CUDA tensors")
     params = [p for m in mods[0::2] for p in (m.weight, m.bias)]
     return _TrainForward.apply(x, tuple(mods), *params)
+
+
+# ----------------------------------------------------------------------------------------------
+# The same for per-agent policies (opt-in: PPOLearner(fused_multi=True) / MSC_FUSED_MULTI_GRAD=1): the P
+# same-shaped actors (or critics) over rows [n, P, L] as one autograd function -- multi_forward forward, so
+# policy p's output is mlp3_forward's on its own rows bit for bit, and ONE msc_mlp_relu_backward_multi call
+# backward (csrc/mlp_backward.hip's multi kernels), whose gradients are per policy bit for bit those of
+# msc_mlp_relu_backward on the policy's gathered rows. Not covered: what train_forward does not cover.
+# ----------------------------------------------------------------------------------------------
+def fused_multi_default() -> bool:
+    """MSC_FUSED_MULTI_GRAD=1 turns the multi-policy MLP backward on where PPOLearner is built with
+    fused_multi=None."""
+    return os.environ.get("MSC_FUSED_MULTI_GRAD", "0") == "1"
+
+
+# msc_mlp_relu_backward_multi_plan's list (include/marlsc.h)
+BWD_MULTI_PLAN_KEYS = ("supported", "group_policies", "groups", "rounds", "slices", "round_tiles", "workspace_bytes")
+
+
+def multi_backward_plan(n_rows: int, n_policies: int, in_dim: int, hidden1: int, hidden2: int, out_dim: int) -> Dict[str, int]:
+    """msc_mlp_relu_backward_multi_plan (no GPU is touched): whether the call exists for these sizes, the policies
+    per set of launches G and the groups, and per policy the rounds, the slices per round and the row tiles of a
+    full round -- the single-policy geometry of n_rows / n_policies rows -- and the workspace bytes."""
+    buf = (C.c_int64 * len(BWD_MULTI_PLAN_KEYS))()
+    n = abi.lib().msc_mlp_relu_backward_multi_plan(int(n_rows), int(n_policies), int(in_dim), int(hidden1), int(hidden2),
+                                                   int(out_dim), buf, len(BWD_MULTI_PLAN_KEYS))
+    if n < 0:
+        abi.check(n)
+    return dict(zip(BWD_MULTI_PLAN_KEYS, (int(v) for v in buf)))
+
+
+def multi_backward_workspace_bytes(n_rows: int, n_policies: int, in_dim: int, hidden1: int, hidden2: int, out_dim: int) -> int:
+    """msc_mlp_relu_backward_multi_workspace: G x the single-policy bytes of n_rows / n_policies rows (monotone in
+    n_rows, capped), -1 where the single query is or for a policy count that is not 1..64 or does not divide n_rows."""
+    return int(abi.lib().msc_mlp_relu_backward_multi_workspace(int(n_rows), int(n_policies), int(in_dim), int(hidden1),
+                                                               int(hidden2), int(out_dim)))
+
+
+def multi_trainable(mods_list) -> bool:
+    """True when multi_train_forward covers mods_list: multi_layers accepts it (same form and shapes, 1..64
+    policies), every list passes trainable, and there are at most 32 outputs. A network that is no layer
+    sequence (a GRU) is not covered."""
+    mods_list = list(mods_list)
+    if not all(isinstance(m, (nn.Sequential, list, tuple)) for m in mods_list):
+        return False
+    mods_list = [list(m) for m in mods_list]
+    if multi_layers(mods_list) == 0 or mods_list[0][-1].out_features > MAX_OUT:
+        return False
+    return all(trainable(mods) for mods in mods_list)
+
+
+def _multi_bwd_pack(mods_list, nl: int, cur):
+    """(w2tp [P, ...] or None, w3 [P, KO, H_last], b1 [P, H1], b2 [P, H2] or None) for the multi backward, cached as
+    multi_pack caches the forward's: keyed on every policy's (data_ptr, _version), rebuilt only when one changes."""
+    lins = [mods[0::2] for mods in mods_list]
+    weights = tuple(p for ls in lins for m in ls for p in (m.weight, m.bias))
+
+    def build():
+        w2tp = torch.stack([pack_w2t(ls[1].weight) for ls in lins]).contiguous() if nl == 3 else None
+        w3 = torch.stack([ls[-1].weight.detach().float() for ls in lins]).contiguous()
+        b1 = torch.stack([ls[0].bias.detach().float() for ls in lins]).contiguous()
+        b2 = torch.stack([ls[1].bias.detach().float() for ls in lins]).contiguous() if nl == 3 else None
+        return (w2tp, w3, b1, b2)
+
+    return _cached_pack(mods_list[0][0], ("multi_bwd", len(mods_list)), weights, cur, build)
+
+
+def multi_backward(mods_list, x: torch.Tensor, d_out: torch.Tensor, *, scale: float = 1.0, grads=None):
+    """One msc_mlp_relu_backward_multi call: the gradients of P policies' parameters (mods_list as accepted by
+    multi_trainable) for the upstream gradient d_out [..., P, KO] at the inputs x [..., P, L] (f32 CUDA). Returns,
+    per policy, the tuple in parameter order (w1, b1[, w2, b2], w3, b3): views g[p] of the stacked outputs
+    [P, ...], each contiguous and in its parameter's shape. grads given (the 4 or 6 stacked contiguous f32
+    tensors): the call adds to them, and the views are of them."""
+    mods_list = [list(m) for m in mods_list]
+    nl = multi_layers(mods_list)
+    if nl == 0:
+        raise ValueError("no multi-policy kernel for these layer sequences (see multi_layers)")
+    NP = len(mods_list)
+    l1, l3 = mods_list[0][0], mods_list[0][-1]
+    L, H1, KO = l1.in_features, l1.out_features, l3.out_features
+    H2 = mods_list[0][2].out_features if nl == 3 else 0
+    if x.dim() < 2 or tuple(x.shape[-2:]) != (NP, L) or d_out.dim() < 2 or tuple(d_out.shape[-2:]) != (NP, KO):
+        raise ValueError(f"x / d_out must be [..., {NP}, {L}] / [..., {NP}, {KO}], not {tuple(x.shape)} / {tuple(d_out.shape)}")
+    xf, df = _rows(x, L), _rows(d_out, KO)
+    n = xf.shape[0]
+    if df.shape[0] != n:
+        raise ValueError(f"d_out has {df.shape[0]} rows for {n} rows of x")
+    cur = torch.cuda.current_stream(xf.device)
+    w1p, w2p = multi_pack(mods_list, None, cur)[:2]
+    w2tp, w3, b1, b2 = _multi_bwd_pack(mods_list, nl, cur)
+    shapes = [tuple(p.shape) for m in mods_list[0][0::2] for p in (m.weight, m.bias)]
+    accumulate = grads is not None
+    if grads is None:
+        grads = tuple(torch.empty((NP,) + s, dtype=torch.float32, device=xf.device) for s in shapes)
+    elif len(grads) != len(shapes) or any(not (g.is_cuda and g.dtype == torch.float32 and g.is_contiguous()
+                                               and tuple(g.shape) == (NP,) + s) for g, s in zip(grads, shapes)):
+        raise ValueError("grads must be contiguous float32 CUDA tensors [P, ...] in the parameters' shapes")
+    ws = _bwd_workspace(xf.device, multi_backward_workspace_bytes(n, NP, L, H1, H2, KO)) if n > 0 else None
+    g = list(grads)
+    gw2, gb2 = (g[2], g[3]) if nl == 3 else (None, None)
+    abi.check(abi.lib().msc_mlp_relu_backward_multi(
+        _vp(xf), n, NP, L, H1, H2, KO, _vp(w1p), _vp(b1), _vp(w2p), _vp(b2), _vp(w2tp), _vp(w3), _vp(df), C.c_float(scale),
+        1 if accumulate else 0, _vp(g[0]), _vp(g[1]), _vp(gw2), _vp(gb2), _vp(g[-2]), _vp(g[-1]), _vp(ws),
+        C.c_void_p(cur.cuda_stream)))
+    return [tuple(t[p] for t in g) for p in range(NP)]
+
+
+class _MultiTrainForward(torch.autograd.Function):
+    """P policies' forward through the multi inference kernel; all their parameters enter as inputs (policy by
+    policy, each in parameter order), so autograd hands every one its gradient."""
+
+    @staticmethod
+    def forward(ctx, x, mods_list, *params):
+        ctx.mods_list = mods_list
+        ctx.save_for_backward(x, *params)
+        return multi_forward(mods_list, x)
+
+    @staticmethod
+    def backward(ctx, g):
+        x = ctx.saved_tensors[0]
+        per_policy = multi_backward(ctx.mods_list, x, g)
+        return (None, None) + tuple(t for gp in per_policy for t in gp)
+
+
+def multi_train_forward(mods_list, x: torch.Tensor) -> torch.Tensor:
+    """P same-shaped MLPs (mods_list as accepted by multi_layers, at most 32 outputs) applied to x [n, P, L] under
+    autograd -> [n, P, KO]: msc_mlp{3,2}_relu_multi now (policy p's rows equal mlp3_forward's and train_forward's
+    on them bit for bit), one msc_mlp_relu_backward_multi call in backward(). x is a leaf of the graph. Refusals as
+    train_forward's: RuntimeError for non-CUDA, non-float32 or gradient-requiring input and for parameters that are
+    not float32 CUDA tensors, ValueError for layer sequences without a kernel."""
+    mods_list = [list(m) for m in mods_list]
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise RuntimeError("multi_train_forward: x must be a CUDA tensor (the fused MLP backward is a HIP kernel; run "
+                           f"the torch layers on {getattr(x, 'device', type(x).__name__)})")
+    if x.dtype != torch.float32:
+        raise RuntimeError(f"multi_train_forward: x must be torch.float32, not {x.dtype}")
+    if x.requires_grad:
+        raise RuntimeError("multi_train_forward: x requires a gradient, and the fused backward computes none for its input")
+    if multi_layers(mods_list) == 0:
+        raise ValueError("no multi-policy kernel for these layer sequences (see multi_layers)")
+    if not multi_trainable(mods_list):
+        raise RuntimeError("multi_train_forward: the parameters must be float32 CUDA tensors")
+    if x.dim() != 3:
+        raise ValueError(f"multi_train_forward: x must be [n, {len(mods_list)}, L], not {tuple(x.shape)}")
+    params = [p for mods in mods_list for m in mods[0::2] for p in (m.weight, m.bias)]
+    return _MultiTrainForward.apply(x, tuple(tuple(m) for m in mods_list), *params)

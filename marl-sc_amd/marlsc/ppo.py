@@ -455,7 +455,7 @@ class PPOLearner:
 
     def __init__(self, module: MultiAgentActorCritic, cfg: PPOConfig, *, seed: int = 0,
                  fused_loss: Optional[bool] = None, fused_mlp: Optional[bool] = None,
-                 fused_opt: Optional[bool] = None):
+                 fused_opt: Optional[bool] = None, fused_multi: Optional[bool] = None):
         """fused_loss: the loss, its statistics and its gradients from the msc_ppo_loss kernel
         (marlsc/ppo_loss.py) instead of ppo_loss under autograd; None reads MSC_FUSED_LOSS (default off).
         fused_mlp: the plain MLP actors and critics (mlp.trainable: the fused inference kernels' ReLU family,
@@ -467,15 +467,24 @@ class PPOLearner:
         msc_adam_clip_step call over every parameter tensor (marlsc/optim.py:FusedClipAdam, which is then
         `self.opt`, with torch.optim.Adam's state_dict format) instead of torch's norm clip per policy and
         torch.optim.Adam.step (clip_and_step); None reads MSC_FUSED_OPT (default off). It covers every network.
+        fused_multi: per-agent policies (not shared, not recurrent, no mu/sigma head) whose minibatches have equal
+        lengths train their P actors, and their P critics, through one mlp.multi_train_forward each -- one stacked
+        row gather, one msc_mlp{3,2}_relu_multi launch forward and one msc_mlp_relu_backward_multi call backward
+        per net kind instead of P of each -- where mlp.multi_trainable covers the P networks; bit for bit what
+        fused_mlp gives policy by policy. A net kind it does not cover keeps the path fused_mlp gives it, and a
+        module it does not cover at all makes it a no-op. A switch of its own: None reads MSC_FUSED_MULTI_GRAD
+        (default off), and fused_mlp alone still makes one call per network.
         Every switch needs the module on a CUDA device and raises RuntimeError otherwise."""
         self.module, self.cfg = module, cfg
         self.fused_loss = fused_loss_default() if fused_loss is None else bool(fused_loss)
         self.fused_mlp = mlp3.fused_mlp_default() if fused_mlp is None else bool(fused_mlp)
         self.fused_opt = fused_opt_default() if fused_opt is None else bool(fused_opt)
+        self.fused_multi = mlp3.fused_multi_default() if fused_multi is None else bool(fused_multi)
         dev = next(module.parameters()).device
         for on, switch, kernel in ((self.fused_loss, "fused_loss", "fused PPO loss"),
                                    (self.fused_mlp, "fused_mlp", "fused MLP backward"),
-                                   (self.fused_opt, "fused_opt", "fused clip + Adam step")):
+                                   (self.fused_opt, "fused_opt", "fused clip + Adam step"),
+                                   (self.fused_multi, "fused_multi", "multi-policy MLP backward")):
             if on and dev.type != "cuda":
                 raise RuntimeError(f"PPOLearner({switch}=True): the {kernel} is a HIP kernel and needs the module "
                                    f"on a CUDA device, not {dev}")
@@ -506,23 +515,54 @@ class PPOLearner:
             return mlp3.train_forward(net, x)
         return net(x)
 
-    def _forward(self, policy: "AgentModule", obs: torch.Tensor, rows: torch.Tensor):
-        """(mean, log_std, values) of `policy` on batch rows (flat ids s * W + w of obs [S, W, L])."""
+    def _multi_outputs(self, obs: torch.Tensor, rows: Sequence[torch.Tensor]):
+        """fused_multi: per policy (actor output or None, critic output or None) from one mlp.multi_train_forward
+        over all the policies' actors and one over their critics, on one stacked gather x [n, P, L] of the
+        policies' rows; None where a net kind is not covered (mlp.multi_trainable). None as a whole when the
+        switch does not apply: a shared, recurrent or mu/sigma-head module, or row tensors of unequal lengths."""
+        m, rc = self.module, self.module.rc
+        if m.shared or getattr(m, "recurrent", False) or m.head_mode or len({int(r.numel()) for r in rows}) != 1:
+            return None
+        if not (obs.is_cuda and obs.dtype == torch.float32 and not obs.requires_grad):
+            return None
+        nets = [[p.actor for p in m.policies], [p.critic for p in m.policies]]
+        kinds = [k for k, ns in zip((rc.actor_obs_type, rc.critic_obs_type), nets) if mlp3.multi_trainable(ns)]
+        if not kinds:
+            return None
+        S, W, L = obs.shape
+        idx = torch.stack(list(rows), dim=1)                                        # [n, P]
+        local = obs.reshape(S * W, L)[idx]                                          # [n, P, L]
+        full = None
+        if "global" in kinds:
+            full = torch.cat([local, obs.reshape(S, W * L)[torch.div(idx, W, rounding_mode="floor")]], dim=-1)
+        outs = [mlp3.multi_train_forward(ns, full if kind == "global" else local).unbind(1)
+                if mlp3.multi_trainable(ns) else [None] * len(rows)
+                for kind, ns in zip((rc.actor_obs_type, rc.critic_obs_type), nets)]
+        return list(zip(*outs))
+
+    def _forward(self, policy: "AgentModule", obs: torch.Tensor, rows: torch.Tensor, pre=(None, None)):
+        """(mean, log_std, values) of `policy` on batch rows (flat ids s * W + w of obs [S, W, L]). pre: the
+        policy's (actor output, critic output) where _multi_outputs has computed them, None where not."""
         rc = self.module.rc
         S, W, L = obs.shape
-        local = obs.reshape(S * W, L)[rows]
-        full = None
-        if rc.actor_obs_type == "global" or rc.critic_obs_type == "global":
-            full = torch.cat([local, obs[torch.div(rows, W, rounding_mode="floor")].reshape(-1, W * L)], dim=-1)
+        mean, values = pre
+        local = full = None
+        if mean is None or values is None:
+            local = obs.reshape(S * W, L)[rows]
+            kinds = ([rc.actor_obs_type] if mean is None else []) + ([rc.critic_obs_type] if values is None else [])
+            if "global" in kinds:
+                full = torch.cat([local, obs[torch.div(rows, W, rounding_mode="floor")].reshape(-1, W * L)], dim=-1)
         if policy.head_mode:  # state-dependent log_std from the head, no free parameter
             mean, log_std = policy.dist(full if rc.actor_obs_type == "global" else local)
         else:
-            mean = self._mlp(policy.actor, full if rc.actor_obs_type == "global" else local)
+            if mean is None:
+                mean = self._mlp(policy.actor, full if rc.actor_obs_type == "global" else local)
             log_std = torch.clamp(policy.log_std, min=rc.logstd_floor).expand_as(mean)
         # (a mu/sigma-head module keeps the torch layers as a whole, critic included)
-        critic = policy.critic if policy.head_mode else (lambda x: self._mlp(policy.critic, x))
-        values = critic(full if rc.critic_obs_type == "global" else local).squeeze(-1)
-        return mean, log_std, values
+        if values is None:
+            critic = policy.critic if policy.head_mode else (lambda x: self._mlp(policy.critic, x))
+            values = critic(full if rc.critic_obs_type == "global" else local)
+        return mean, log_std, values.squeeze(-1)
 
     # -- GRU networks: a training sample is a sequence (chunk c, env e, agent w) of S = max_seq_len
     # consecutive rollout steps, id (c E + e) W + w; its rows are the flat ids ((c S + s) E + e) W + w --
@@ -631,11 +671,12 @@ class PPOLearner:
         gradient all-reduce, clip and step. The losses go through `stats` (new_stats), which adds up their
         statistics. It keeps nothing of update(): the same rows by hand give the same step."""
         total = None
+        pre = self._multi_outputs(obs, rows) if self.fused_multi and seq is None else None
         for j, (pol, idx) in enumerate(zip(self.module.policies, rows)):
             if seq is not None:
                 mean, log_std, values, idx = self._seq_forward(pol, obs, seq, idx)
             else:
-                mean, log_std, values = self._forward(pol, obs, idx)
+                mean, log_std, values = self._forward(pol, obs, idx, (None, None) if pre is None else pre[j])
             loss = stats.loss(j, mean, log_std, values, flat, idx, self.kl_coeffs[j])
             total = loss if total is None else total + loss
         self.opt.zero_grad(set_to_none=True)
@@ -751,10 +792,10 @@ class PPOTrainer:
                  rollout_len: Optional[int] = None, device: int = 0, env_meta: Optional[Dict[str, Any]] = None,
                  eval_seed: Optional[int] = None, multi_mlp: Optional[bool] = None,
                  fused_loss: Optional[bool] = None, fused_mlp: Optional[bool] = None,
-                 fused_opt: Optional[bool] = None):
+                 fused_opt: Optional[bool] = None, fused_multi: Optional[bool] = None):
         """multi_mlp: passed to MultiAgentActorCritic (per-agent policies in one launch; None reads
-        MSC_MULTI_MLP). fused_loss / fused_mlp / fused_opt: passed to PPOLearner (None reads
-        MSC_FUSED_LOSS / MSC_FUSED_MLP_GRAD / MSC_FUSED_OPT)."""
+        MSC_MULTI_MLP). fused_loss / fused_mlp / fused_opt / fused_multi: passed to PPOLearner (None reads
+        MSC_FUSED_LOSS / MSC_FUSED_MLP_GRAD / MSC_FUSED_OPT / MSC_FUSED_MULTI_GRAD)."""
         from .seeding import SeedManager
         from .spec import EnvSpec
         from .vec_env import VecInventoryEnv
@@ -797,7 +838,7 @@ class PPOTrainer:
             for p in self.module.parameters():
                 dist.broadcast(p.data, src=0)
         self.learner = PPOLearner(self.module, cfg, seed=self.train_seed + self.rank, fused_loss=fused_loss,
-                                  fused_mlp=fused_mlp, fused_opt=fused_opt)
+                                  fused_mlp=fused_mlp, fused_opt=fused_opt, fused_multi=fused_multi)
         # advantages standardised per module (RLlib's GAE connector): one group for the shared policy,
         # one per agent otherwise
         # one noise seed for every rank: the noise is keyed by global env id (msc_normal_keyed)

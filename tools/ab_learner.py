@@ -20,11 +20,21 @@ Adam.step; opt_fused: one FusedClipAdam.step). The per-agent row's step_torch / 
 step_fused_mlp clip per policy, as the learner does: they are not comparable with the same rows of
 profiles/{ppo_loss,mlp_backward,adam_clip}/ab_learner.txt, which a hand-written step with one clip_grad_norm_
 call over all policies produced (profiles/learner_loop/ab_learner.txt is the first record of this step).
+The per-agent rows (8 ippo.yaml policies, 8 mappo.yaml policies, 16 ippo.yaml policies -- the C5 agent count --
+at 800 rows each) also run step_fused_mlp_opt_multi: all four switches on, the P actors and the P critics
+through one mlp.multi_train_forward each (msc_mlp_relu_backward_multi, PPOLearner(fused_multi=True), opt-in),
+compared with step_fused_mlp_opt of the same run. A fourth split times the MLP backward alone at these shapes on
+one d_out: bwd_single is P mlp.mlp_backward calls on each policy's gathered rows (the gather not timed), bwd_multi
+one mlp.multi_backward call.
 The variants are alternated in one process after a warm-up; each sample is one step between two device
 events, the device idle before the first (synchronised). Medians, the 5th .. 95th percentile and the range.
 
   python tools/ab_learner.py [--rounds 100] [--rounds-large 20] [--warmup 10] [--out profiles/learner_loop/ab_learner.txt]
-  python tools/ab_learner.py --count-launches   # a few steps of each variant at 800 rows, for a kernel trace"""
+  python tools/ab_learner.py --per-agent-only    # the per-agent rows alone
+  python tools/ab_learner.py --count-launches   # a few steps of each variant at 800 rows, for a kernel trace
+  python tools/ab_learner.py --count-launches --variant step_fused_mlp_opt_multi --steps 12
+      # --steps steps of one per-agent variant (8 ippo.yaml policies): the kernel records of two traces with
+      # different --steps, subtracted and divided by the difference in steps, are the launches of one step"""
 import argparse
 import json
 import sys
@@ -64,23 +74,26 @@ def _setup(name: str, S: int, W: int, L: int, K: int, shared: bool = True):
     return cfg, m, obs, batch
 
 
-# the step variants: name -> (fused_loss, fused_mlp, fused_opt) of the PPOLearner that runs them
-SWITCHES = {"step_torch": (False, False, False), "step_fused": (True, False, False), "step_mlp": (False, True, False),
-            "step_fused_mlp": (True, True, False), "step_torch_opt": (False, False, True),
-            "step_fused_opt": (True, False, True), "step_fused_mlp_opt": (True, True, True)}
+# the step variants: name -> (fused_loss, fused_mlp, fused_opt, fused_multi) of the PPOLearner that runs them
+SWITCHES = {"step_torch": (False, False, False, False), "step_fused": (True, False, False, False),
+            "step_mlp": (False, True, False, False), "step_fused_mlp": (True, True, False, False),
+            "step_torch_opt": (False, False, True, False), "step_fused_opt": (True, False, True, False),
+            "step_fused_mlp_opt": (True, True, True, False)}
+MULTI = "step_fused_mlp_opt_multi"  # per-agent rows only (a no-op on a shared policy)
 
 
 class Steps:
     """PPOLearner.minibatch_step on fixed rows (one index tensor per policy), one learner per switch combination
     over the same module, each with its own optimizer and statistics accumulator."""
 
-    def __init__(self, cfg, m, obs, batch, rows):
+    def __init__(self, cfg, m, obs, batch, rows, multi=False):
         from marlsc.ppo import PPOLearner
         self.cfg, self.obs, self.rows = cfg, obs, rows
+        self.switches = dict(SWITCHES, **({MULTI: (True, True, True, True)} if multi else {}))
         S, W = obs.shape[0], obs.shape[1]
         self.flat = {k: v.reshape(S * W, *v.shape[2:]) for k, v in batch.items()}
-        self.learners = {k: PPOLearner(m, cfg, seed=0, fused_loss=fl, fused_mlp=fm, fused_opt=fo)
-                         for k, (fl, fm, fo) in SWITCHES.items()}
+        self.learners = {k: PPOLearner(m, cfg, seed=0, fused_loss=fl, fused_mlp=fm, fused_opt=fo, fused_multi=mu)
+                         for k, (fl, fm, fo, mu) in self.switches.items()}
         self.stats = {k: ln.new_stats(obs.device) for k, ln in self.learners.items()}
         self.dev_stats = torch.zeros(5, dtype=torch.float64, device="cuda")
         # the clip and the Adam step alone, on the gradients the last backward left in place
@@ -89,7 +102,34 @@ class Steps:
 
     def step_variants(self):
         return {k: (lambda k=k: self.learners[k].minibatch_step(self.obs, None, self.flat, self.rows, self.stats[k]))
-                for k in SWITCHES}
+                for k in self.switches}
+
+    def backward_variants(self):
+        """The MLP backward alone, actors then critics, on one upstream gradient: P single-policy calls on each
+        policy's gathered rows against one multi-policy call on the rows where they lie."""
+        from marlsc import mlp as M
+        ln = self.learners[MULTI]
+        S, W, L = self.obs.shape
+        idx = torch.stack(list(self.rows), dim=1)
+        local = self.obs.reshape(S * W, L)[idx]
+        full = torch.cat([local, self.obs.reshape(S, W * L)[torch.div(idx, W, rounding_mode="floor")]], dim=-1)
+        jobs = []
+        for kind, nets in ((ln.module.rc.actor_obs_type, [list(p.actor) for p in ln.module.policies]),
+                           (ln.module.rc.critic_obs_type, [list(p.critic) for p in ln.module.policies])):
+            x = (full if kind == "global" else local).contiguous()
+            d = torch.randn(*x.shape[:2], nets[0][-1].out_features, device="cuda") / x.shape[0]
+            xs, ds = [x[:, p].contiguous() for p in range(len(nets))], [d[:, p].contiguous() for p in range(len(nets))]
+            jobs.append((nets, x, d, xs, ds))
+
+        def single():
+            for nets, _, _, xs, ds in jobs:
+                for net, xp, dp in zip(nets, xs, ds):
+                    M.mlp_backward(net, xp, dp)
+
+        def multi():
+            for nets, x, d, _, _ in jobs:
+                M.multi_backward(nets, x, d)
+        return {"bwd_single": single, "bwd_multi": multi}
 
     def outputs(self):
         with torch.no_grad():
@@ -146,8 +186,19 @@ def main() -> int:
     ap.add_argument("--out", type=str, default=None)
     ap.add_argument("--count-launches", action="store_true",
                     help="run 10 torch steps, then 10 fused steps of the ippo networks at 800 rows and exit")
+    ap.add_argument("--variant", type=str, default=None, help="with --count-launches: one per-agent variant instead")
+    ap.add_argument("--steps", type=int, default=10, help="with --count-launches --variant: steps to run")
+    ap.add_argument("--per-agent-only", action="store_true", help="skip the shared-policy rows")
     args = ap.parse_args()
     W, K, L = 8, 5, _local_obs_dim()
+    if args.count_launches and args.variant:
+        cfg, m, obs, batch = _setup("ippo", 8000, W, L, K, shared=False)
+        st = Steps(cfg, m, obs, batch, [torch.randperm(8000, device="cuda")[:800] * W + w for w in range(W)], multi=True)
+        fn = st.step_variants()[args.variant]
+        for _ in range(args.steps):
+            fn()
+        torch.cuda.synchronize()
+        return 0
     if args.count_launches:
         cfg, m, obs, batch = _setup("ippo", 8000, W, L, K)
         st = Steps(cfg, m, obs, batch, [torch.randperm(8000 * W, device="cuda")[:800]])
@@ -159,7 +210,7 @@ def main() -> int:
     lines = [f"device: {torch.cuda.get_device_name(0)}   warmup {args.warmup}, variants alternated, one step per sample, us",
              f"observation width {L} (C3, with the warehouse one-hot), K = {K}, {W} agents on one shared policy"]
     results = []
-    for name in ("ippo", "mappo"):
+    for name in () if args.per_agent_only else ("ippo", "mappo"):
         for S, rows, rounds in ((8000, 800, args.rounds), (32768, 32768 * W, args.rounds_large)):
             cfg, m, obs, batch = _setup(name, S, W, L, K)
             st = Steps(cfg, m, obs, batch, [torch.randperm(S * W, device="cuda")[:rows]])
@@ -185,26 +236,36 @@ def main() -> int:
             results.append(res)
             del st, leaves, cfg, m, obs, batch
             torch.cuda.empty_cache()
-    # per-agent policies: 8 ippo.yaml policies, 800 rows each out of each agent's 8,000
-    cfg, m, obs, batch = _setup("ippo", 8000, W, L, K, shared=False)
-    idx = [torch.randperm(8000, device="cuda")[:800] * W + w for w in range(W)]
-    st = Steps(cfg, m, obs, batch, idx)
-    t = _time(st.step_variants(), args.rounds, args.warmup)
-    t.update(_time({"opt_torch": st.opt_torch, "opt_fused": st.opt_fused}, args.rounds, args.warmup))
-    res = {"config": "ippo per-agent", "rows": 800, "policies": W, "rounds": args.rounds}
-    lines.append(f"ippo.yaml networks, {W} per-agent policies, minibatches of 800 rows each, {args.rounds} rounds")
-    for k, v in t.items():
-        res[k] = {"median_us": float(np.median(v)), "p05_us": float(np.percentile(v, 5)),
-                  "p95_us": float(np.percentile(v, 95)), "min_us": float(v.min()), "max_us": float(v.max())}
-        lines.append(f"  {k:18s} median {res[k]['median_us']:9.1f}   p05 {res[k]['p05_us']:9.1f}   p95 "
-                     f"{res[k]['p95_us']:9.1f}   range {res[k]['min_us']:.1f} .. {res[k]['max_us']:.1f}")
-    for k, base in (("step_mlp", "step_torch"), ("step_fused_mlp", "step_fused"), ("step_fused_mlp", "step_torch")):
-        res[f"{base}_over_{k}"] = res[base]["median_us"] / res[k]["median_us"]
-        lines.append(f"  {base} / {k} = {res[f'{base}_over_{k}']:.3f}")
-    res["opt_torch_over_fused"] = res["opt_torch"]["median_us"] / res["opt_fused"]["median_us"]
-    lines.append(f"  opt: torch / fused = {res['opt_torch_over_fused']:.3f}")
-    _opt_lines(res, lines)
-    results.append(res)
+    # per-agent policies, 800 rows each out of each agent's 8,000
+    for name, W in (("ippo", 8), ("mappo", 8), ("ippo", 16)):
+        cfg, m, obs, batch = _setup(name, 8000, W, L, K, shared=False)
+        idx = [torch.randperm(8000, device="cuda")[:800] * W + w for w in range(W)]
+        st = Steps(cfg, m, obs, batch, idx, multi=True)
+        t = _time(st.step_variants(), args.rounds, args.warmup)
+        t.update(_time({"opt_torch": st.opt_torch, "opt_fused": st.opt_fused}, args.rounds, args.warmup))
+        t.update(_time(st.backward_variants(), args.rounds, args.warmup))
+        res = {"config": f"{name} per-agent", "rows": 800, "policies": W, "rounds": args.rounds}
+        lines.append(f"{name}.yaml networks, {W} per-agent policies, minibatches of 800 rows each, {args.rounds} rounds")
+        for k, v in t.items():
+            res[k] = {"median_us": float(np.median(v)), "p05_us": float(np.percentile(v, 5)),
+                      "p95_us": float(np.percentile(v, 95)), "min_us": float(v.min()), "max_us": float(v.max())}
+            lines.append(f"  {k:24s} median {res[k]['median_us']:9.1f}   p05 {res[k]['p05_us']:9.1f}   p95 "
+                         f"{res[k]['p95_us']:9.1f}   range {res[k]['min_us']:.1f} .. {res[k]['max_us']:.1f}")
+        for k, base in (("step_mlp", "step_torch"), ("step_fused_mlp", "step_fused"), ("step_fused_mlp", "step_torch")):
+            res[f"{base}_over_{k}"] = res[base]["median_us"] / res[k]["median_us"]
+            lines.append(f"  {base} / {k} = {res[f'{base}_over_{k}']:.3f}")
+        res["opt_torch_over_fused"] = res["opt_torch"]["median_us"] / res["opt_fused"]["median_us"]
+        lines.append(f"  opt: torch / fused = {res['opt_torch_over_fused']:.3f}")
+        _opt_lines(res, lines)
+        for k, base in ((MULTI, "step_fused_mlp_opt"), ("bwd_multi", "bwd_single")):
+            res[f"{base}_over_{k}"] = res[base]["median_us"] / res[k]["median_us"]
+            clear = res[k]["p95_us"] < res[base]["p05_us"]
+            res[f"{k}_p95_below_{base}_p05"] = bool(clear)
+            lines.append(f"  {base} / {k} = {res[f'{base}_over_{k}']:.3f}   ({k} p95 {res[k]['p95_us']:.1f} "
+                         f"{'<' if clear else '>='} {base} p05 {res[base]['p05_us']:.1f})")
+        results.append(res)
+        del st, cfg, m, obs, batch
+        torch.cuda.empty_cache()
     text = "\n".join(lines) + "\n"
     print(text)
     print(json.dumps(results))
