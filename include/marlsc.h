@@ -411,6 +411,37 @@ int msc_ppo_loss(const msc_ppo_loss_desc* desc, const float* mean, const float* 
                  int32_t k, float* grad_mean, float* grad_log_std, float* grad_values, float* total, double* stats,
                  void* workspace, msc_stream_t stream);
 
+/* msc_ppo_loss for n_policies policies (per-agent modules) in one call: two launches instead of two per
+ * policy. Per policy bit for bit msc_ppo_loss: policy p's totals[p], stats[p], and its slices of the three
+ * gradients are the bits the single call gives for (n_rows, k) on policy p's contiguous slices with
+ * kl_coeff = kl_coeffs[p] (the same per-row arithmetic, row-to-block mapping and float64 summation order).
+ * Every policy has n_rows rows. Layouts (float32 device buffers unless said):
+ *   mean / grad_mean [n_rows][n_policies][k], values / grad_values [n_rows][n_policies];
+ *   log_std [n_policies][k] (log_std_rows = 1: one shared row per policy, clamped by the caller;
+ *   grad_log_std the row-summed [n_policies][k]) or [n_rows][n_policies][k] (log_std_rows = 0, grad_log_std
+ *   the same shape);
+ *   idx device int64 [n_rows][n_policies]: idx[i][p] is the batch row of policy p's i-th sample, in [0, B),
+ *   repeats and rows shared between policies allowed, not checked. idx NULL: b = i n_policies + p, the
+ *   batch interleaved like the outputs;
+ *   actions [B][k], logp_old / advantages / value_targets [B], mean_old / log_std_old [B][k]: the flat batch
+ *   columns msc_ppo_loss reads, one set for all policies.
+ * kl_coeffs: HOST double[n_policies], one coefficient per policy (a learner adapts one per module), read
+ * during the call and not kept; NULL without use_kl. desc->kl_coeff is ignored; every other field of desc
+ * holds for all policies. Outputs: totals device f32[n_policies]; stats device f64[n_policies][5], stored or
+ * with accumulate_stats added to, per policy as msc_ppo_loss does.
+ * workspace: msc_ppo_loss_multi_workspace(n_rows, n_policies, k) = n_policies x msc_ppo_loss_workspace(n_rows,
+ * k) bytes (-1 for a bad shape). The call launches two kernels on `stream`, synchronises nothing, and
+ * neither allocates nor keeps memory. No atomics: equal calls give equal bits.
+ * Errors (msc_last_error, nothing launched): n_rows <= 0, n_policies outside [1, 64], k outside [1, 128], a
+ * null desc or required pointer (idx may be null), use_kl with null kl_coeffs, mean_old or log_std_old. */
+int64_t msc_ppo_loss_multi_workspace(int64_t n_rows, int32_t n_policies, int32_t k);
+int msc_ppo_loss_multi(const msc_ppo_loss_desc* desc, const double* kl_coeffs, const float* mean,
+                       const float* log_std, const float* values, const int64_t* idx, const float* actions,
+                       const float* logp_old, const float* advantages, const float* value_targets,
+                       const float* mean_old, const float* log_std_old, int64_t n_rows, int32_t n_policies,
+                       int32_t k, float* grad_mean, float* grad_log_std, float* grad_values, float* totals,
+                       double* stats, void* workspace, msc_stream_t stream);
+
 /* The learner's gradient clip and Adam step in one call: torch.nn.utils.clip_grad_norm_ per group (a group
  * is one policy: RLlib's learner clips each module's gradients by its own global norm) followed by
  * torch.optim.Adam.step (no weight decay, no amsgrad) over every tensor of every group, up to rounding order.

@@ -937,6 +937,49 @@ int msc_ppo_loss(const msc_ppo_loss_desc* desc, const float* mean, const float* 
   return 0;
 }
 
+int64_t msc_ppo_loss_multi_workspace(int64_t n_rows, int32_t n_policies, int32_t k) {
+  return n_rows >= 1 && n_policies >= 1 && n_policies <= PL_MAX_POLICIES && k >= 1 && k <= 128
+             ? n_policies * ppo_loss_workspace_bytes(n_rows, k)
+             : -1;
+}
+
+int msc_ppo_loss_multi(const msc_ppo_loss_desc* desc, const double* kl_coeffs, const float* mean, const float* log_std,
+                       const float* values, const int64_t* idx, const float* actions, const float* logp_old,
+                       const float* advantages, const float* value_targets, const float* mean_old,
+                       const float* log_std_old, int64_t n_rows, int32_t n_policies, int32_t k, float* grad_mean,
+                       float* grad_log_std, float* grad_values, float* totals, double* stats, void* workspace,
+                       msc_stream_t stream) {
+  if (!desc) return set_err(-1, "msc_ppo_loss_multi: null desc");
+  if (n_rows <= 0 || n_policies < 1 || n_policies > PL_MAX_POLICIES || k < 1 || k > 128)
+    return set_err(-1, "msc_ppo_loss_multi: bad shape (n_rows %lld must be >= 1, n_policies %d in [1, %d], k %d in [1, 128])",
+                   (long long)n_rows, n_policies, PL_MAX_POLICIES, k);
+  if (!mean || !log_std || !values || !actions || !logp_old || !advantages || !value_targets || !grad_mean ||
+      !grad_log_std || !grad_values || !totals || !stats || !workspace)
+    return set_err(-1, "msc_ppo_loss_multi: null argument");
+  if (desc->use_kl && (!kl_coeffs || !mean_old || !log_std_old))
+    return set_err(-1, "msc_ppo_loss_multi: use_kl needs kl_coeffs, mean_old and log_std_old");
+  if (desc->log_std_rows != 0 && desc->log_std_rows != 1)
+    return set_err(-1, "msc_ppo_loss_multi: log_std_rows %d must be 1 (one shared row per policy) or 0 (per row)",
+                   desc->log_std_rows);
+  PpoLossMultiArgs m;
+  PpoLossArgs& a = m.a;
+  a.mean = mean, a.log_std = log_std, a.values = values, a.idx = idx;
+  a.actions = actions, a.logp_old = logp_old, a.advantages = advantages, a.value_targets = value_targets;
+  a.mean_old = mean_old, a.log_std_old = log_std_old;
+  a.grad_mean = grad_mean, a.grad_log_std = grad_log_std, a.grad_values = grad_values;
+  a.n = n_rows, a.K = k, a.use_kl = desc->use_kl ? 1 : 0, a.shared = desc->log_std_rows;
+  a.lo = (float)(1.0 - desc->clip_param), a.hi = (float)(1.0 + desc->clip_param);
+  a.vf_clip = (float)desc->vf_clip_param, a.c_v = (float)desc->vf_loss_coeff, a.c_e = (float)desc->entropy_coeff;
+  a.kl_coeff = 0.0f;
+  a.beta = (float)desc->hysteretic_beta;
+  a.inv_n = 1.0f / (float)n_rows;
+  m.P = n_policies;
+  for (int p = 0; p < PL_MAX_POLICIES; p++)
+    m.kl_coeff[p] = desc->use_kl && p < n_policies ? (float)kl_coeffs[p] : 0.0f;
+  HIP_TRY(launch_ppo_loss_multi(m, desc->accumulate_stats ? 1 : 0, totals, stats, workspace, (hipStream_t)stream));
+  return 0;
+}
+
 int64_t msc_adam_clip_workspace(int32_t n_tensors, int64_t total_elems) {
   return n_tensors >= 1 && total_elems >= 0 ? adam_clip_workspace_bytes(n_tensors, total_elems) : -1;
 }

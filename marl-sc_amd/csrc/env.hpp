@@ -339,6 +339,17 @@ int ppo_loss_rows_per_block(int32_t K);
 int64_t ppo_loss_workspace_bytes(int64_t n, int32_t K);
 hipError_t launch_ppo_loss(const PpoLossArgs& a, int accumulate, float* total, double* stats, void* workspace,
                            hipStream_t st);
+// the multi-policy form (msc_ppo_loss_multi): `a` with the operands stacked per policy -- mean / grad_mean
+// [n][P][K], values / grad_values / idx [n][P], log_std and its gradient [P][K] when shared, else [n][P][K];
+// a.kl_coeff unused, one coefficient per policy instead
+constexpr int PL_MAX_POLICIES = 64;
+struct PpoLossMultiArgs {
+  PpoLossArgs a;
+  int32_t P;
+  float kl_coeff[PL_MAX_POLICIES];
+};
+hipError_t launch_ppo_loss_multi(const PpoLossMultiArgs& m, int accumulate, float* totals, double* stats,
+                                 void* workspace, hipStream_t st);
 // adam_clip.hip: the per-group gradient clip and the Adam step over a host table of tensors (msc_adam_clip_step)
 int adam_clip_chunk();           // elements per block
 int adam_clip_table_capacity();  // table entries per launch

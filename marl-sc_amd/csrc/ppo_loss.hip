@@ -31,6 +31,14 @@
 // ppo_loss_finalize_kernel (one block, same stream) adds the partials in block order inside up to 16
 // segments and the segment sums in segment order. No atomics: the grid and the segments are functions of
 // (n, K) alone, so the results are bitwise reproducible.
+//
+// Multi-policy form (msc_ppo_loss_multi): P policies' losses in one launch, grid (ppo_loss_grid(n, K), P) with
+// blockIdx.y the policy. Output row i of policy p is element o = i P + p of the stacked [n][P][K] / [n][P]
+// operands (and of idx; b = o without one); a shared log_std is row p of [P][K]. The rows of a policy map to
+// blocks, lanes and loop steps exactly as in the single launch for (n, K), ppo_loss_rows is the one body of
+// both, the partials are [P][grid][PL_PS] and the finalize launch has one block per policy, each the
+// single-policy finalize on its policy's partials: per policy every output has the single launch's bits.
+// kl_coeff alone differs per policy and travels in the kernel arguments (PL_MAX_POLICIES floats).
 #include <hip/hip_runtime.h>
 #include <math.h>
 
@@ -50,8 +58,11 @@ __host__ __device__ constexpr int pl_group(int K) {
   return g;
 }
 
-template <int G, int E>
-__global__ __launch_bounds__(PL_BS) void ppo_loss_kernel(const PpoLossArgs a, double* __restrict__ part) {
+// The block's share of one policy's rows. MULTI: policy p of P, operands stacked [n][P][..]; otherwise P = 1,
+// p = 0 and the element index is the row.
+template <int G, int E, bool MULTI>
+__device__ __forceinline__ void ppo_loss_rows(const PpoLossArgs& a, const int64_t P, const int64_t p,
+                                              const float kl_coeff, double* __restrict__ part) {
   constexpr int RPB = PL_BS / G;
   constexpr float HALF_LOG2PI = 0.91893853320467274178f, ENT_CONST = 1.41893853320467274178f;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -61,12 +72,13 @@ __global__ __launch_bounds__(PL_BS) void ppo_loss_kernel(const PpoLossArgs a, do
   double acc_ls[E];
 #pragma unroll
   for (int e = 0; e < E; e++) acc_ls[e] = 0.0;
-  const float gk = a.kl_coeff * a.inv_n, ge = a.c_e * a.inv_n, gv = a.c_v * a.inv_n;
+  const float gk = kl_coeff * a.inv_n, ge = a.c_e * a.inv_n, gv = a.c_v * a.inv_n;
 
   for (int64_t base = (int64_t)blockIdx.x * RPB; base < a.n; base += (int64_t)gridDim.x * RPB) {
     const int64_t row = base + tid / G;
     const bool act = row < a.n;
-    const int64_t b = act ? (a.idx ? a.idx[row] : row) : 0;
+    const int64_t o = MULTI ? row * P + p : row;  // the row's element of mean / values / idx and their gradients
+    const int64_t b = act ? (a.idx ? a.idx[o] : o) : 0;
     float lp = 0.0f, ent = 0.0f, kl = 0.0f;
     float dmu[E], dls[E], kmu[E], kls[E];
 #pragma unroll
@@ -74,8 +86,8 @@ __global__ __launch_bounds__(PL_BS) void ppo_loss_kernel(const PpoLossArgs a, do
       const int k = k0 + 64 * e;
       dmu[e] = dls[e] = kmu[e] = kls[e] = 0.0f;
       if (act && k < K) {
-        const float m = a.mean[row * K + k];
-        const float ls = a.shared ? a.log_std[k] : a.log_std[row * K + k];
+        const float m = a.mean[o * K + k];
+        const float ls = a.shared ? a.log_std[(MULTI ? p * K : 0) + k] : a.log_std[o * K + k];
         const float ac = a.actions[b * K + k];
         const float std_ = expf(ls);
         const float var = std_ * std_;
@@ -121,7 +133,7 @@ __global__ __launch_bounds__(PL_BS) void ppo_loss_kernel(const PpoLossArgs a, do
       else if (s1 > s2) w = inr ? A : 0.0f;
       else w = 0.5f * A + (inr ? 0.5f * A : 0.0f);
       g = (-a.inv_n * w) * r;
-      const float dv = a.values[row] - a.value_targets[b];
+      const float dv = a.values[o] - a.value_targets[b];
       const float vf = dv * dv;
       vfc = fminf(fmaxf(vf, 0.0f), a.vf_clip);
       gval = (vf >= 0.0f && vf <= a.vf_clip) ? gv * (2.0f * dv) : 0.0f;
@@ -137,13 +149,13 @@ __global__ __launch_bounds__(PL_BS) void ppo_loss_kernel(const PpoLossArgs a, do
           gm += gk * kmu[e];
           gl += gk * kls[e];
         }
-        a.grad_mean[row * K + k] = gm;
+        a.grad_mean[o * K + k] = gm;
         if (a.shared) acc_ls[e] += (double)gl;
-        else a.grad_log_std[row * K + k] = gl;
+        else a.grad_log_std[o * K + k] = gl;
       }
     }
     if (act && k0 == 0) {
-      a.grad_values[row] = gval;
+      a.grad_values[o] = gval;
       acc[0] += (double)row_loss;
       acc[1] += (double)(-surr);
       acc[2] += (double)vfc;
@@ -181,14 +193,25 @@ __global__ __launch_bounds__(PL_BS) void ppo_loss_kernel(const PpoLossArgs a, do
   }
 }
 
+template <int G, int E>
+__global__ __launch_bounds__(PL_BS) void ppo_loss_kernel(const PpoLossArgs a, double* __restrict__ part) {
+  ppo_loss_rows<G, E, false>(a, 1, 0, a.kl_coeff, part);
+}
+
+template <int G, int E>
+__global__ __launch_bounds__(PL_BS) void ppo_loss_multi_kernel(const PpoLossMultiArgs m, double* __restrict__ part) {
+  const int p = blockIdx.y;
+  ppo_loss_rows<G, E, true>(m.a, m.P, p, m.kl_coeff[p], part + (int64_t)p * gridDim.x * PL_PS);
+}
+
 // one block: every column of the partials summed over the blocks in a fixed order. The 256 threads are Q
 // segments x Wc column slots (Wc the power of two >= the columns in use, at least 16: Q = 16 at K <= 8, 1 at
 // K > 120); a thread adds its segment's blocks in block order, 16 loads in flight at a time, and the
 // column's thread of segment 0 adds the Q segment sums in segment order.
-__global__ __launch_bounds__(PL_BS) void ppo_loss_finalize_kernel(const double* __restrict__ part, int nblk, int64_t n,
-                                                                int K, int shared, int accumulate, float kl_coeff,
-                                                                float* __restrict__ grad_log_std,
-                                                                float* __restrict__ total, double* __restrict__ stats) {
+__device__ __forceinline__ void ppo_loss_finalize(const double* __restrict__ part, int nblk, int64_t n, int K,
+                                                  int shared, int accumulate, float kl_coeff,
+                                                  float* __restrict__ grad_log_std, float* __restrict__ total,
+                                                  double* __restrict__ stats) {
   __shared__ double seg[PL_BS];
   __shared__ double sm[PL_NSTAT];
   const int t = threadIdx.x;
@@ -231,6 +254,23 @@ __global__ __launch_bounds__(PL_BS) void ppo_loss_finalize_kernel(const double* 
   }
 }
 
+__global__ __launch_bounds__(PL_BS) void ppo_loss_finalize_kernel(const double* __restrict__ part, int nblk, int64_t n,
+                                                                int K, int shared, int accumulate, float kl_coeff,
+                                                                float* __restrict__ grad_log_std,
+                                                                float* __restrict__ total, double* __restrict__ stats) {
+  ppo_loss_finalize(part, nblk, n, K, shared, accumulate, kl_coeff, grad_log_std, total, stats);
+}
+
+// block p: policy p's partials into grad_log_std[p] (shared rows), totals[p] and stats[p]
+__global__ __launch_bounds__(PL_BS) void ppo_loss_finalize_multi_kernel(const PpoLossMultiArgs m,
+                                                                      const double* __restrict__ part, int nblk,
+                                                                      int accumulate, float* __restrict__ totals,
+                                                                      double* __restrict__ stats) {
+  const int p = blockIdx.x;
+  ppo_loss_finalize(part + (int64_t)p * nblk * PL_PS, nblk, m.a.n, m.a.K, m.a.shared, accumulate, m.kl_coeff[p],
+                    m.a.grad_log_std + (int64_t)p * m.a.K, totals + p, stats + (int64_t)p * PL_NSTAT);
+}
+
 int ppo_loss_rows_per_block(int32_t K) { return PL_BS / pl_group(K); }
 int ppo_loss_grid(int64_t n, int32_t K) {
   const int64_t rpb = ppo_loss_rows_per_block(K);
@@ -241,24 +281,43 @@ int64_t ppo_loss_workspace_bytes(int64_t n, int32_t K) {
   return (int64_t)ppo_loss_grid(n, K) * PL_PS * (int64_t)sizeof(double);
 }
 
+// one (G, E) instantiation of KERNEL for K columns
+#define PL_DISPATCH(K_, LAUNCH)      \
+  do {                               \
+    const int G_ = pl_group(K_);     \
+    if ((K_) > 64) LAUNCH(64, 2);    \
+    else if (G_ == 64) LAUNCH(64, 1); \
+    else if (G_ == 32) LAUNCH(32, 1); \
+    else if (G_ == 16) LAUNCH(16, 1); \
+    else if (G_ == 8) LAUNCH(8, 1);  \
+    else if (G_ == 4) LAUNCH(4, 1);  \
+    else if (G_ == 2) LAUNCH(2, 1);  \
+    else LAUNCH(1, 1);               \
+  } while (0)
+
 hipError_t launch_ppo_loss(const PpoLossArgs& a, int accumulate, float* total, double* stats, void* workspace,
                            hipStream_t st) {
   const int nb = ppo_loss_grid(a.n, a.K);
   double* part = (double*)workspace;
-  const int G = pl_group(a.K);
 #define PL_LAUNCH(GG, EE) \
   hipLaunchKernelGGL((ppo_loss_kernel<GG, EE>), dim3(nb), dim3(PL_BS), 0, st, a, part)
-  if (a.K > 64) PL_LAUNCH(64, 2);
-  else if (G == 64) PL_LAUNCH(64, 1);
-  else if (G == 32) PL_LAUNCH(32, 1);
-  else if (G == 16) PL_LAUNCH(16, 1);
-  else if (G == 8) PL_LAUNCH(8, 1);
-  else if (G == 4) PL_LAUNCH(4, 1);
-  else if (G == 2) PL_LAUNCH(2, 1);
-  else PL_LAUNCH(1, 1);
+  PL_DISPATCH(a.K, PL_LAUNCH);
 #undef PL_LAUNCH
   hipLaunchKernelGGL(ppo_loss_finalize_kernel, dim3(1), dim3(PL_BS), 0, st, part, nb, a.n, a.K, a.shared, accumulate,
                      a.kl_coeff, a.grad_log_std, total, stats);
+  return hipGetLastError();
+}
+
+hipError_t launch_ppo_loss_multi(const PpoLossMultiArgs& m, int accumulate, float* totals, double* stats,
+                                 void* workspace, hipStream_t st) {
+  const int nb = ppo_loss_grid(m.a.n, m.a.K);
+  double* part = (double*)workspace;
+#define PL_LAUNCH(GG, EE) \
+  hipLaunchKernelGGL((ppo_loss_multi_kernel<GG, EE>), dim3(nb, m.P), dim3(PL_BS), 0, st, m, part)
+  PL_DISPATCH(m.a.K, PL_LAUNCH);
+#undef PL_LAUNCH
+  hipLaunchKernelGGL(ppo_loss_finalize_multi_kernel, dim3(m.P), dim3(PL_BS), 0, st, m, part, nb, accumulate, totals,
+                     stats);
   return hipGetLastError();
 }
 

@@ -17,7 +17,7 @@ __all__ = [
     "CPPOConfig", "CPPOTrainer", "CentralizedRolloutEnv", "CentralizedActorCritic",
     "RandomPolicy", "ConstantPolicy", "BaseStockPolicy", "AdaptiveBaseStockPolicy", "newsvendor_levels",
     "rollout_episodes", "calibrate_demand", "validation_sweep", "evaluate_levels", "optimize_levels",
-    "fused_ppo_loss",
+    "fused_ppo_loss", "fused_ppo_loss_multi",
 ]
 
 _BASELINES = ("RandomPolicy", "ConstantPolicy", "BaseStockPolicy", "AdaptiveBaseStockPolicy", "newsvendor_levels",
@@ -37,9 +37,9 @@ def __getattr__(name):  # torch-dependent modules load lazily
     if name in ("CPPOConfig", "CPPOTrainer", "CentralizedRolloutEnv", "CentralizedActorCritic"):
         from . import cppo
         return getattr(cppo, name)
-    if name == "fused_ppo_loss":
-        from .ppo_loss import fused_ppo_loss
-        return fused_ppo_loss
+    if name in ("fused_ppo_loss", "fused_ppo_loss_multi"):
+        from . import ppo_loss
+        return getattr(ppo_loss, name)
     if name in _BASELINES:
         from . import baselines
         return getattr(baselines, name)

@@ -170,6 +170,10 @@ def lib() -> C.CDLL:
     L.msc_ppo_loss_workspace.restype = C.c_int64
     L.msc_ppo_loss.argtypes = [P(MscPpoLossDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int64, C.c_int32, vp, vp,
                                vp, vp, vp, vp, vp]
+    L.msc_ppo_loss_multi_workspace.argtypes = [C.c_int64, C.c_int32, C.c_int32]
+    L.msc_ppo_loss_multi_workspace.restype = C.c_int64
+    L.msc_ppo_loss_multi.argtypes = [P(MscPpoLossDesc), dp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int64, C.c_int32,
+                                     C.c_int32, vp, vp, vp, vp, vp, vp, vp]
     L.msc_adam_clip_workspace.argtypes = [C.c_int32, C.c_int64]
     L.msc_adam_clip_workspace.restype = C.c_int64
     L.msc_adam_clip_geometry.argtypes = [ip, ip]
@@ -242,6 +246,7 @@ EXPORTED_SYMBOLS = [
     "msc_env_create", "msc_env_destroy", "msc_env_dims", "msc_env_kernel_choice", "msc_env_plan", "msc_env_set_option", "msc_env_alloc_tail_entry", "msc_env_ea_memory", "msc_env_reset", "msc_env_step", "msc_env_generate_demand", "msc_env_set_pipelining", "msc_env_set_chain_priority", "msc_env_set_episode_ahead", "msc_env_set_timing", "msc_env_read_timing", "msc_env_read_timing_ea", "msc_env_work_counters", "msc_env_obs_flat",
     "msc_env_read_state", "msc_env_state_bytes", "msc_env_save_state", "msc_env_load_state", "msc_env_check",
     "msc_env_set_episode_counters", "msc_gae", "msc_adv_normalize", "msc_gae_grouped", "msc_adv_normalize_grouped", "msc_ppo_loss_workspace", "msc_ppo_loss",
+    "msc_ppo_loss_multi_workspace", "msc_ppo_loss_multi",
     "msc_adam_clip_workspace", "msc_adam_clip_geometry", "msc_adam_clip_step", "msc_gaussian_sample", "msc_mlp3_w3_layout", "msc_mlp_plan", "msc_mlp3_relu_forward", "msc_mlp2_relu_forward",
     "msc_mlp3_relu_forward_sampled", "msc_mlp2_relu_forward_sampled",
     "msc_mlp_musigma_layout", "msc_mlp3_relu_musigma", "msc_mlp2_relu_musigma",

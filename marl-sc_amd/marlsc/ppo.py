@@ -53,7 +53,7 @@ import torch.nn as nn
 from . import dist as mdist
 from . import mlp as mlp3
 from .optim import FusedClipAdam, fused_opt_default
-from .ppo_loss import STAT_KEYS, fused_loss_default, fused_ppo_loss
+from .ppo_loss import STAT_KEYS, fused_loss_default, fused_multi_loss_default, fused_ppo_loss, fused_ppo_loss_multi
 from .rollout import (LOG_STD_MIN, PolicyNets, RecurrentAPI, RolloutCollector, RolloutConfig, check_gru_config,
                       check_head_config, fused_actor_sample, gaussian_sample, head_sample, mlp_forward, network_types,
                       split_global_mlp)
@@ -436,6 +436,11 @@ class _DeviceStats:
     def loss(self, j, mean, log_std, values, flat, idx, kl_coeff):
         return fused_ppo_loss(self.cfg, mean, log_std, values, flat, idx, kl_coeff, stats=self.dev[j])[0]
 
+    def loss_multi(self, mean, log_std, values, flat, idx, kl_coeffs):
+        """Every module's loss in one call on the stacked outputs: the sum of loss(j, ...) over the modules, each
+        module's statistics added to its row of the buffer."""
+        return fused_ppo_loss_multi(self.cfg, mean, log_std, values, flat, idx, kl_coeffs, stats=self.dev)[0]
+
     def end_step(self) -> None:
         pass
 
@@ -444,6 +449,20 @@ class _DeviceStats:
         keys = ["policy_loss", "vf_loss", "entropy"] + (["mean_kl"] if self.cfg.use_kl_loss else []) + ["total_loss"]
         out = {k: float(host[:, STAT_KEYS.index(k)].sum()) / self.n_modules / max(n, 1) for k in keys}
         return out, [float(x) for x in host[:, STAT_KEYS.index("mean_kl")]]
+
+
+class _StackPolicies(torch.autograd.Function):
+    """torch.stack(pieces, dim=1) whose backward hands every policy's piece back contiguous, as the per-policy loss
+    hands it: a torch layer's weight gradient is a GEMM on that piece, and on a strided slice of the stacked gradient
+    it sums in another order (same value, other bits)."""
+
+    @staticmethod
+    def forward(ctx, *pieces):
+        return torch.stack(pieces, dim=1)
+
+    @staticmethod
+    def backward(ctx, g):
+        return tuple(p.contiguous() for p in g.unbind(1))
 
 
 class PPOLearner:
@@ -455,7 +474,8 @@ class PPOLearner:
 
     def __init__(self, module: MultiAgentActorCritic, cfg: PPOConfig, *, seed: int = 0,
                  fused_loss: Optional[bool] = None, fused_mlp: Optional[bool] = None,
-                 fused_opt: Optional[bool] = None, fused_multi: Optional[bool] = None):
+                 fused_opt: Optional[bool] = None, fused_multi: Optional[bool] = None,
+                 fused_multi_loss: Optional[bool] = None):
         """fused_loss: the loss, its statistics and its gradients from the msc_ppo_loss kernel
         (marlsc/ppo_loss.py) instead of ppo_loss under autograd; None reads MSC_FUSED_LOSS (default off).
         fused_mlp: the plain MLP actors and critics (mlp.trainable: the fused inference kernels' ReLU family,
@@ -474,17 +494,25 @@ class PPOLearner:
         fused_mlp gives policy by policy. A net kind it does not cover keeps the path fused_mlp gives it, and a
         module it does not cover at all makes it a no-op. A switch of its own: None reads MSC_FUSED_MULTI_GRAD
         (default off), and fused_mlp alone still makes one call per network.
+        fused_multi_loss: with fused_loss, per-agent policies (not shared, not recurrent, all with or all without
+        the mu/sigma head) whose minibatches have equal lengths get their P losses from one msc_ppo_loss_multi
+        call (ppo_loss.fused_ppo_loss_multi) on the stacked network outputs -- fused_multi's stacked outputs as
+        they are, per-policy outputs stacked -- instead of P msc_ppo_loss calls; bit for bit what fused_loss gives
+        policy by policy. Without fused_loss, or on a module or a step it does not cover, it is a no-op. A switch
+        of its own: None reads MSC_FUSED_MULTI_LOSS (default off).
         Every switch needs the module on a CUDA device and raises RuntimeError otherwise."""
         self.module, self.cfg = module, cfg
         self.fused_loss = fused_loss_default() if fused_loss is None else bool(fused_loss)
         self.fused_mlp = mlp3.fused_mlp_default() if fused_mlp is None else bool(fused_mlp)
         self.fused_opt = fused_opt_default() if fused_opt is None else bool(fused_opt)
         self.fused_multi = mlp3.fused_multi_default() if fused_multi is None else bool(fused_multi)
+        self.fused_multi_loss = fused_multi_loss_default() if fused_multi_loss is None else bool(fused_multi_loss)
         dev = next(module.parameters()).device
         for on, switch, kernel in ((self.fused_loss, "fused_loss", "fused PPO loss"),
                                    (self.fused_mlp, "fused_mlp", "fused MLP backward"),
                                    (self.fused_opt, "fused_opt", "fused clip + Adam step"),
-                                   (self.fused_multi, "fused_multi", "multi-policy MLP backward")):
+                                   (self.fused_multi, "fused_multi", "multi-policy MLP backward"),
+                                   (self.fused_multi_loss, "fused_multi_loss", "multi-policy PPO loss")):
             if on and dev.type != "cuda":
                 raise RuntimeError(f"PPOLearner({switch}=True): the {kernel} is a HIP kernel and needs the module "
                                    f"on a CUDA device, not {dev}")
@@ -515,11 +543,12 @@ class PPOLearner:
             return mlp3.train_forward(net, x)
         return net(x)
 
-    def _multi_outputs(self, obs: torch.Tensor, rows: Sequence[torch.Tensor]):
-        """fused_multi: per policy (actor output or None, critic output or None) from one mlp.multi_train_forward
-        over all the policies' actors and one over their critics, on one stacked gather x [n, P, L] of the
-        policies' rows; None where a net kind is not covered (mlp.multi_trainable). None as a whole when the
-        switch does not apply: a shared, recurrent or mu/sigma-head module, or row tensors of unequal lengths."""
+    def _multi_stacked(self, obs: torch.Tensor, rows: Sequence[torch.Tensor]):
+        """fused_multi: (idx [n, P], (actor outputs [n, P, K] or None, critic outputs [n, P, 1] or None)) from one
+        mlp.multi_train_forward over all the policies' actors and one over their critics, on one stacked gather
+        x [n, P, L] of the policies' rows idx; None where a net kind is not covered (mlp.multi_trainable). None as
+        a whole when the switch does not apply: a shared, recurrent or mu/sigma-head module, or row tensors of
+        unequal lengths."""
         m, rc = self.module, self.module.rc
         if m.shared or getattr(m, "recurrent", False) or m.head_mode or len({int(r.numel()) for r in rows}) != 1:
             return None
@@ -535,10 +564,46 @@ class PPOLearner:
         full = None
         if "global" in kinds:
             full = torch.cat([local, obs.reshape(S, W * L)[torch.div(idx, W, rounding_mode="floor")]], dim=-1)
-        outs = [mlp3.multi_train_forward(ns, full if kind == "global" else local).unbind(1)
-                if mlp3.multi_trainable(ns) else [None] * len(rows)
-                for kind, ns in zip((rc.actor_obs_type, rc.critic_obs_type), nets)]
-        return list(zip(*outs))
+        return idx, tuple(mlp3.multi_train_forward(ns, full if kind == "global" else local)
+                          if mlp3.multi_trainable(ns) else None
+                          for kind, ns in zip((rc.actor_obs_type, rc.critic_obs_type), nets))
+
+    def _multi_outputs(self, obs: torch.Tensor, rows: Sequence[torch.Tensor]):
+        """_multi_stacked cut per policy: (actor output or None, critic output or None) for every policy, or None."""
+        st = self._multi_stacked(obs, rows)
+        if st is None:
+            return None
+        return list(zip(*[[None] * len(rows) if o is None else o.unbind(1) for o in st[1]]))
+
+    def _multi_loss_applies(self, seq, rows: Sequence[torch.Tensor], stats) -> bool:
+        """fused_multi_loss takes this step: the fused loss on (its statistics on the device), a per-agent module
+        that is not recurrent, rows of equal lengths and one head mode for all policies."""
+        m = self.module
+        return (self.fused_multi_loss and self.fused_loss and hasattr(stats, "loss_multi") and seq is None
+                and not m.shared and not getattr(m, "recurrent", False) and len(m.policies) <= mlp3.MULTI_MAX_POLICIES
+                and len({int(r.numel()) for r in rows}) == 1 and len({bool(p.head_mode) for p in m.policies}) == 1)
+
+    def _multi_loss(self, obs: torch.Tensor, flat: Dict[str, torch.Tensor], rows: Sequence[torch.Tensor], stats):
+        """The sum of every policy's loss from one stats.loss_multi call. The stacked [n, P, out] outputs of
+        _multi_stacked go in as they are, with its idx; a net kind that came per policy (torch layers, fused_mlp
+        alone, mu/sigma heads) is stacked on dim 1 (_StackPolicies). The free log_std rows are stacked and clamped once."""
+        m, rc = self.module, self.module.rc
+        st = self._multi_stacked(obs, rows) if self.fused_multi else None
+        idx, (mean, values) = st if st is not None else (torch.stack(list(rows), dim=1), (None, None))
+        log_std = None
+        if mean is None or values is None:
+            cut = [(None if o is None else o.unbind(1)) for o in (mean, values)]
+            per = [self._forward(pol, obs, r, tuple(None if c is None else c[j] for c in cut))
+                   for j, (pol, r) in enumerate(zip(m.policies, rows))]
+            if mean is None:
+                mean = _StackPolicies.apply(*[o[0] for o in per])
+                if m.policies[0].head_mode:
+                    log_std = _StackPolicies.apply(*[o[1] for o in per])
+            if values is None:
+                values = _StackPolicies.apply(*[o[2] for o in per])
+        if log_std is None:
+            log_std = torch.clamp(torch.stack([pol.log_std for pol in m.policies]), min=rc.logstd_floor)
+        return stats.loss_multi(mean, log_std, values, flat, idx, self.kl_coeffs)
 
     def _forward(self, policy: "AgentModule", obs: torch.Tensor, rows: torch.Tensor, pre=(None, None)):
         """(mean, log_std, values) of `policy` on batch rows (flat ids s * W + w of obs [S, W, L]). pre: the
@@ -670,6 +735,9 @@ class PPOLearner:
         the flat batch columns (sequence ids when seq is given); the sum of the module losses, backward, the
         gradient all-reduce, clip and step. The losses go through `stats` (new_stats), which adds up their
         statistics. It keeps nothing of update(): the same rows by hand give the same step."""
+        if self._multi_loss_applies(seq, rows, stats):
+            total = self._multi_loss(obs, flat, rows, stats)
+            return self._backward_and_step(total, stats)
         total = None
         pre = self._multi_outputs(obs, rows) if self.fused_multi and seq is None else None
         for j, (pol, idx) in enumerate(zip(self.module.policies, rows)):
@@ -679,6 +747,9 @@ class PPOLearner:
                 mean, log_std, values = self._forward(pol, obs, idx, (None, None) if pre is None else pre[j])
             loss = stats.loss(j, mean, log_std, values, flat, idx, self.kl_coeffs[j])
             total = loss if total is None else total + loss
+        self._backward_and_step(total, stats)
+
+    def _backward_and_step(self, total: torch.Tensor, stats) -> None:
         self.opt.zero_grad(set_to_none=True)
         total.backward()
         allreduce_grads([p for p in self.module.parameters() if p.grad is not None])
@@ -792,10 +863,12 @@ class PPOTrainer:
                  rollout_len: Optional[int] = None, device: int = 0, env_meta: Optional[Dict[str, Any]] = None,
                  eval_seed: Optional[int] = None, multi_mlp: Optional[bool] = None,
                  fused_loss: Optional[bool] = None, fused_mlp: Optional[bool] = None,
-                 fused_opt: Optional[bool] = None, fused_multi: Optional[bool] = None):
+                 fused_opt: Optional[bool] = None, fused_multi: Optional[bool] = None,
+                 fused_multi_loss: Optional[bool] = None):
         """multi_mlp: passed to MultiAgentActorCritic (per-agent policies in one launch; None reads
-        MSC_MULTI_MLP). fused_loss / fused_mlp / fused_opt / fused_multi: passed to PPOLearner (None reads
-        MSC_FUSED_LOSS / MSC_FUSED_MLP_GRAD / MSC_FUSED_OPT / MSC_FUSED_MULTI_GRAD)."""
+        MSC_MULTI_MLP). fused_loss / fused_mlp / fused_opt / fused_multi / fused_multi_loss: passed to
+        PPOLearner (None reads MSC_FUSED_LOSS / MSC_FUSED_MLP_GRAD / MSC_FUSED_OPT / MSC_FUSED_MULTI_GRAD /
+        MSC_FUSED_MULTI_LOSS)."""
         from .seeding import SeedManager
         from .spec import EnvSpec
         from .vec_env import VecInventoryEnv
@@ -838,7 +911,8 @@ class PPOTrainer:
             for p in self.module.parameters():
                 dist.broadcast(p.data, src=0)
         self.learner = PPOLearner(self.module, cfg, seed=self.train_seed + self.rank, fused_loss=fused_loss,
-                                  fused_mlp=fused_mlp, fused_opt=fused_opt, fused_multi=fused_multi)
+                                  fused_mlp=fused_mlp, fused_opt=fused_opt, fused_multi=fused_multi,
+                                  fused_multi_loss=fused_multi_loss)
         # advantages standardised per module (RLlib's GAE connector): one group for the shared policy,
         # one per agent otherwise
         # one noise seed for every rank: the noise is keyed by global env id (msc_normal_keyed)

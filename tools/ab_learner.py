@@ -26,6 +26,11 @@ through one mlp.multi_train_forward each (msc_mlp_relu_backward_multi, PPOLearne
 compared with step_fused_mlp_opt of the same run. A fourth split times the MLP backward alone at these shapes on
 one d_out: bwd_single is P mlp.mlp_backward calls on each policy's gathered rows (the gather not timed), bwd_multi
 one mlp.multi_backward call.
+They also run step_fused_mlp_opt_multi_loss: all five switches on, the P losses from one msc_ppo_loss_multi call on
+the stacked outputs (PPOLearner(fused_multi_loss=True), opt-in), compared with step_fused_mlp_opt_multi of the same
+run. A fifth split times the loss with its backward alone from given stacked network outputs: loss_single is P
+fused_ppo_loss calls on each policy's contiguous slices (the slicing not timed), summed, and one backward();
+loss_multi one fused_ppo_loss_multi call and its backward().
 The variants are alternated in one process after a warm-up; each sample is one step between two device
 events, the device idle before the first (synchronised). Medians, the 5th .. 95th percentile and the range.
 
@@ -74,12 +79,14 @@ def _setup(name: str, S: int, W: int, L: int, K: int, shared: bool = True):
     return cfg, m, obs, batch
 
 
-# the step variants: name -> (fused_loss, fused_mlp, fused_opt, fused_multi) of the PPOLearner that runs them
+# the step variants: name -> (fused_loss, fused_mlp, fused_opt, fused_multi[, fused_multi_loss]) of the PPOLearner that
+# runs them
 SWITCHES = {"step_torch": (False, False, False, False), "step_fused": (True, False, False, False),
             "step_mlp": (False, True, False, False), "step_fused_mlp": (True, True, False, False),
             "step_torch_opt": (False, False, True, False), "step_fused_opt": (True, False, True, False),
             "step_fused_mlp_opt": (True, True, True, False)}
 MULTI = "step_fused_mlp_opt_multi"  # per-agent rows only (a no-op on a shared policy)
+MULTI_LOSS = "step_fused_mlp_opt_multi_loss"  # the same
 
 
 class Steps:
@@ -89,11 +96,13 @@ class Steps:
     def __init__(self, cfg, m, obs, batch, rows, multi=False):
         from marlsc.ppo import PPOLearner
         self.cfg, self.obs, self.rows = cfg, obs, rows
-        self.switches = dict(SWITCHES, **({MULTI: (True, True, True, True)} if multi else {}))
+        self.switches = dict(SWITCHES, **({MULTI: (True, True, True, True),
+                                           MULTI_LOSS: (True, True, True, True, True)} if multi else {}))
         S, W = obs.shape[0], obs.shape[1]
         self.flat = {k: v.reshape(S * W, *v.shape[2:]) for k, v in batch.items()}
-        self.learners = {k: PPOLearner(m, cfg, seed=0, fused_loss=fl, fused_mlp=fm, fused_opt=fo, fused_multi=mu)
-                         for k, (fl, fm, fo, mu) in self.switches.items()}
+        self.learners = {k: PPOLearner(m, cfg, seed=0, fused_loss=fl, fused_mlp=fm, fused_opt=fo, fused_multi=mu,
+                                       fused_multi_loss=bool(ml))
+                         for k, (fl, fm, fo, mu, *ml) in self.switches.items()}
         self.stats = {k: ln.new_stats(obs.device) for k, ln in self.learners.items()}
         self.dev_stats = torch.zeros(5, dtype=torch.float64, device="cuda")
         # the clip and the Adam step alone, on the gradients the last backward left in place
@@ -130,6 +139,36 @@ class Steps:
             for nets, x, d, _, _ in jobs:
                 M.multi_backward(nets, x, d)
         return {"bwd_single": single, "bwd_multi": multi}
+
+    def loss_variants(self):
+        """The loss with its backward alone, from the P policies' stacked outputs (leaves): P single-policy calls on
+        each policy's contiguous slices, summed as the learner sums them, against one multi-policy call."""
+        from marlsc.ppo_loss import fused_ppo_loss, fused_ppo_loss_multi
+        ln = self.learners[MULTI]
+        pols, rc = ln.module.policies, ln.module.rc
+        with torch.no_grad():
+            outs = [ln._forward(pol, self.obs, r) for pol, r in zip(pols, self.rows)]
+            mean = torch.stack([o[0] for o in outs], dim=1)
+            values = torch.stack([o[2] for o in outs], dim=1)
+            log_std = torch.clamp(torch.stack([pol.log_std for pol in pols]), min=rc.logstd_floor)
+        idx = torch.stack(list(self.rows), dim=1)
+        P = len(pols)
+        kl = [0.2] * P
+        stacked = [t.detach().clone().requires_grad_() for t in (mean, log_std, values)]
+        per = [[t.detach().clone().requires_grad_() for t in (mean[:, p], log_std[p], values[:, p])] for p in range(P)]
+        rows = [r.contiguous() for r in self.rows]
+        dev1, devP = torch.zeros((P, 5), dtype=torch.float64, device="cuda"), torch.zeros((P, 5), dtype=torch.float64, device="cuda")
+
+        def single():
+            total = None
+            for p, (m_, l_, v_) in enumerate(per):
+                loss = fused_ppo_loss(self.cfg, m_, l_, v_, self.flat, rows[p], kl[p], stats=dev1[p])[0]
+                total = loss if total is None else total + loss
+            total.backward()
+
+        def multi():
+            fused_ppo_loss_multi(self.cfg, *stacked, self.flat, idx, kl, stats=devP)[0].backward()
+        return {"loss_single": single, "loss_multi": multi}
 
     def outputs(self):
         with torch.no_grad():
@@ -244,12 +283,13 @@ def main() -> int:
         t = _time(st.step_variants(), args.rounds, args.warmup)
         t.update(_time({"opt_torch": st.opt_torch, "opt_fused": st.opt_fused}, args.rounds, args.warmup))
         t.update(_time(st.backward_variants(), args.rounds, args.warmup))
+        t.update(_time(st.loss_variants(), args.rounds, args.warmup))
         res = {"config": f"{name} per-agent", "rows": 800, "policies": W, "rounds": args.rounds}
         lines.append(f"{name}.yaml networks, {W} per-agent policies, minibatches of 800 rows each, {args.rounds} rounds")
         for k, v in t.items():
             res[k] = {"median_us": float(np.median(v)), "p05_us": float(np.percentile(v, 5)),
                       "p95_us": float(np.percentile(v, 95)), "min_us": float(v.min()), "max_us": float(v.max())}
-            lines.append(f"  {k:24s} median {res[k]['median_us']:9.1f}   p05 {res[k]['p05_us']:9.1f}   p95 "
+            lines.append(f"  {k:30s} median {res[k]['median_us']:9.1f}   p05 {res[k]['p05_us']:9.1f}   p95 "
                          f"{res[k]['p95_us']:9.1f}   range {res[k]['min_us']:.1f} .. {res[k]['max_us']:.1f}")
         for k, base in (("step_mlp", "step_torch"), ("step_fused_mlp", "step_fused"), ("step_fused_mlp", "step_torch")):
             res[f"{base}_over_{k}"] = res[base]["median_us"] / res[k]["median_us"]
@@ -257,7 +297,8 @@ def main() -> int:
         res["opt_torch_over_fused"] = res["opt_torch"]["median_us"] / res["opt_fused"]["median_us"]
         lines.append(f"  opt: torch / fused = {res['opt_torch_over_fused']:.3f}")
         _opt_lines(res, lines)
-        for k, base in ((MULTI, "step_fused_mlp_opt"), ("bwd_multi", "bwd_single")):
+        for k, base in ((MULTI, "step_fused_mlp_opt"), ("bwd_multi", "bwd_single"), (MULTI_LOSS, MULTI),
+                        ("loss_multi", "loss_single")):
             res[f"{base}_over_{k}"] = res[base]["median_us"] / res[k]["median_us"]
             clear = res[k]["p95_us"] < res[base]["p05_us"]
             res[f"{k}_p95_below_{base}_p05"] = bool(clear)
